@@ -7,13 +7,19 @@ Workload (BASELINE.json configs[1] / SURVEY.md section 8d cfg2): UNet2D5_dsbn al
 One step = zero-grad -> forward -> loss -> backward -> (RCCL all-reduce) -> Adam for ONE batch of one
 domain; the domain alternates 0/1 per step.  Inputs are resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--repeats R]
+    python bench.py --gpus N --steps K --warmup W [--repeats R] [--dump-outputs DIR] [--full]
 N > 1: one rank per GPU over RCCL, weak scaling (per-GPU batch fixed).  Either the driver launches the ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) or - when RANK is not in the
 environment - this process starts them itself as a child `torch.distributed.run` BEFORE it touches the GPU, relays rank
 0's JSON line and exits with the child's code.  Every rank checks WORLD_SIZE == --gpus and fails loudly otherwise.
-The K-step timed region (barrier + synchronize on both sides, max over ranks) is run R times (default 5) in the one
-command; `ms_per_step` / `value` are those of the MEDIAN region, min / max are reported beside it.  Rank 0 prints ONE JSON line.
+The K-step timed region (barrier + synchronize on both sides, max over ranks) is run R times (default 1, 5 with --full) in
+the one command; `ms_per_step` / `value` are those of the MEDIAN region, min / max are reported beside it.  Rank 0 prints ONE
+JSON line.
+
+A plain run sets up, warms up, times the regions and prints the line.  --full adds what is measured beside the headline:
+the per-kernel timing pass with its roofline figures, `secondary` (plugin path, configs 4 and 5) and the CPU baseline at one
+rank, the `rccl` / `exposed_comm_ms` measurements with a process group (the --no-* options switch single parts off).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -543,6 +549,26 @@ def secondary():
     return out
 
 
+DUMP_SAMPLE = 1 << 21        # flat positions sampled by dump_outputs (the full buffers are about 90 MB each)
+
+
+def dump_outputs(path, out, ts):
+    """--dump-outputs: what the last timed step handed its caller, written as float32 .npy files under `path` (16 MB in all):
+      loss.npy    the step's return value [total, dice, ce, entropy, class dice...] (TrainStep.step)
+      params.npy  the fp32 master weights after the step's Adam update (net.flat_params)
+      grads.npy   the gradient that update read (TrainStep.gflat)
+    params / grads hold the same DUMP_SAMPLE flat positions, drawn without replacement by numpy's default_rng(0) and sorted,
+    so the files of two runs (or two builds) with the same arguments compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    flat, grad = ts.net.flat_params.detach(), ts.gflat
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    idx_t = torch.from_numpy(idx).to(flat.device)
+    arrays = {"loss": out, "params": flat[idx_t], "grads": grad[idx_t]}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def launch_ranks(n, timeout_s=1500.0, attempts=3):
     """`bench.py --gpus N` without a launcher: start N ranks as a child `python -m torch.distributed.run` (this process has
     not initialised the GPU and never will), relay rank 0's JSON line, return the child's exit code.  The child runs in a
@@ -592,11 +618,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1, 5 with --full)")
     ap.add_argument("--launch", action="store_true", help="start the ranks as a child torch.distributed.run even for --gpus 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` measurements (plugin path, configs 4 and 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: kernel table and rooflines, `secondary`, CPU baseline, "
+                         "`rccl` / exposed communication")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) skip the per-kernel timing pass")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="(--full) skip the `secondary` measurements (plugin path, configs 4 and 5)")
     ap.add_argument("--secondary-part", choices=SECONDARY_PARTS, help="(internal) run ONE secondary measurement and print its JSON")
     args = ap.parse_args()
     if args.secondary_part:
@@ -604,6 +636,8 @@ def main():
         torch.cuda.set_device(dev0)
         print(json.dumps(secondary_part(args.secondary_part, dev0)))
         return
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus < 1 or args.steps < 1 or args.repeats < 1 or args.warmup < 0:
         ap.error("--gpus, --steps, --repeats must be >= 1 and --warmup >= 0")
 
@@ -634,7 +668,7 @@ def main():
     ts = fplx.TrainStep(net, (1.0, 0.0, 0.0, 0.0), True, lr=1e-4, weight_decay=1e-5,
                         milestones=[10000, 20000, 30000, 40000], gamma=0.5)
     batches = [synth_batch(SHAPE, 1000 * rank + d, dev) for d in (0, 1)]
-    timer = None if args.no_kernel_timing else KernelTimer(ops)
+    timer = KernelTimer(ops) if args.full and not args.no_kernel_timing else None
 
     def run(k0, k):
         out = None
@@ -644,7 +678,7 @@ def main():
         return out
 
     run(0, args.warmup)
-    rccl = rccl_report(ts, dev, rank, world) if use_dist else None       # before (and outside) the timed region
+    rccl = rccl_report(ts, dev, rank, world) if use_dist and args.full else None     # before (and outside) the timed region
 
     def timed_region(k0_):
         """EXACTLY --steps steps between barrier + synchronize pairs; -> (seconds on this rank, last step's output)"""
@@ -671,11 +705,13 @@ def main():
         regions = [float(v) for v in tt.tolist()]
     dt = float(np.median(regions))
     loss = float(out[0].item())
+    if args.dump_outputs and rank == 0:             # before anything below runs further steps
+        dump_outputs(args.dump_outputs, out, ts)
     # exposed communication: the same regions with every collective of the step switched off - no gradient
     # buckets, no all-reduce of the loss sums (each rank then differentiates its LOCAL loss: a timing probe, its results are
     # discarded) - AFTER the headline regions; exposed_comm_ms = headline step - this step
     exposed = None
-    if use_dist:
+    if use_dist and args.full:
         red_on, loss_on = ts.reducer.enabled, ts.dist_loss
         ts.reducer.enabled, ts.dist_loss = False, False
         run(k0, 2)
@@ -778,9 +814,9 @@ def main():
             res["roofline_min"] = roof_min
         if ktable:
             res["kernels"] = ktable[:40]
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             res["secondary"] = secondary()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res))
     if use_dist:

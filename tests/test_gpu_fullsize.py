@@ -279,7 +279,7 @@ def test_bench_under_torchrun_exercises_the_rccl_path():
     env = dict(os.environ, FPLX_DDP_FORCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
-           "--warmup", "1", "--no-kernel-timing", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-kernel-timing", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -298,7 +298,7 @@ def test_bench_under_torchrun_exercises_the_rccl_path():
     # the other way: no launcher - `bench.py --gpus 1` runs in-process, and with --launch it starts the rank itself as a child
     # torch.distributed.run (what `bench.py --gpus N`, N > 1, does when RANK is not set) and relays rank 0's line
     env_nolaunch = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    tail = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "2", "--no-kernel-timing", "--no-cpu-baseline"]
+    tail = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "2", "--full", "--no-kernel-timing", "--no-cpu-baseline"]
     for extra in ([], ["--launch"]):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + tail + extra, cwd=root, env=env_nolaunch,
                            capture_output=True, text=True, timeout=600)
@@ -308,6 +308,41 @@ def test_bench_under_torchrun_exercises_the_rccl_path():
         d = json.loads(lines[0])
         assert d["n_gpus"] == 1 and d["steps"] == 2 and d["repeats"] == 2 and d["value"] > 10
         assert ("rccl" in d) == bool(extra)               # in-process single rank: no process group, no rccl object
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`bench.py` without --full: ONE region of exactly --steps timed steps, the headline keys and none of the measurements
+    beside them; --dump-outputs writes the last timed step's loss vector, sampled master weights and gradient as float32
+    .npy files, and a second process with the same arguments writes the same arrays bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FPLX_DDP_FORCE")}
+    dumps = []
+    for run in range(2):
+        out_dir = str(tmp_path / ("run%d" % run))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", out_dir], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["repeats"] == 1
+        assert d["unit"] == "volumes/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["value"] > 10
+        assert d["ms_per_step_min"] == d["ms_per_step"] == d["ms_per_step_max"] > 0
+        assert not {"secondary", "cpu_baseline", "kernels", "roofline", "roofline_hbm", "rccl"} & set(d)
+        arrs = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in ("loss", "params", "grads")}
+        assert sorted(os.listdir(out_dir)) == ["grads.npy", "loss.npy", "params.npy"]
+        assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss"].shape == (6,) and abs(float(arrs["loss"][0]) - d["final_loss"]) < 1e-5
+        assert arrs["params"].shape == arrs["grads"].shape == (1 << 21,) and np.abs(arrs["grads"]).max() > 0
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 def test_config5_full_size_weighted_dual_domain_step():

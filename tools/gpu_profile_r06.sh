@@ -13,9 +13,9 @@ one() {                      # the single file a pass must have produced
   if [ -z "$f" ]; then echo "gpu_profile_r06: no $2 under $1" >&2; exit 3; fi
   echo "$f"
 }
-timeout 900 python bench.py --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"
+timeout 900 python bench.py --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err"
 export FPLX_SIDE_STREAM=0            # one kernel at a time: clean per-launch durations and counters
-PROG="python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-secondary"
+PROG="python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-kernel-timing --no-secondary"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- $PROG > "$O/trace.log" 2>&1
 python tools/trace_summary.py "$(one "$O/trace" '*kernel_trace.csv')" "$O/kernel_trace_by_shape.csv" > "$O/trace_summary.txt"
 cp "$(one "$O/trace" '*kernel_stats.csv')" "$O/bench_kernel_stats.csv"
