@@ -33,6 +33,7 @@ from . import ops
 from .dataset import NiftyDataset, BatchLoader
 from .infer import Inferer
 from .nifti import save_array_as_nifty_volume
+from .postprocess import PostProcessDict
 from .transform import TransformDict, Compose
 from .loss import SegLossDict, make_loss
 from .net import UNet2D5_dsbn
@@ -55,6 +56,8 @@ class SegmentationAgent(object):
         self.net_dict = SegNetDict
         self.loss_dict = None
         self.inferer = None
+        self.postprocessor = None                                          # agent_seg.py:40
+        self.postprocess_dict = PostProcessDict
         self.checkpoint = None
         self.train_loader_1 = self.train_loader_2 = self.test_loader = None
         self.engine_mode = True            # training loops through fplx.TrainStep where network, loss and optimiser are fplx's own
@@ -100,6 +103,11 @@ class SegmentationAgent(object):
 
     def set_inferer(self, inferer):
         self.inferer = inferer
+
+    def set_postprocessor(self, postprocessor):
+        """agent_seg.py:144-151: a callable applied by save_outputs to every predicted volume (numpy uint8 [D, H, W] in,
+        the processed volume out), such as an instance of fplx.postprocess.PostProcess"""
+        self.postprocessor = postprocessor
 
     def set_loaders(self, train_loader_1=None, train_loader_2=None, test_loader=None):
         self.train_loader_1, self.train_loader_2, self.test_loader = train_loader_1, train_loader_2, test_loader
@@ -444,6 +452,10 @@ class SegmentationAgent(object):
 
     # ---- inference (agent_seg.py:834-964)
     def infer(self, mc_passes=6, return_outputs=False):
+        """Predicts every test volume.  Without FPL: returns {name: uint8 argmax mask on the device} - the raw masks, before
+        label_source / label_target conversion and before the post-processor (testing.post_process or set_postprocessor),
+        which both apply only to the files save_outputs writes.  With FPL: the sorted uncertainty list (no post-processing,
+        as in the reference)."""
         cfg = self.config['testing']
         ckpt_names = None
         if 'ckpt_mode' in cfg and self.checkpoint is None:                  # agent_seg.py:854-866
@@ -474,6 +486,9 @@ class SegmentationAgent(object):
         uncertainty_list, outputs = {}, {}
         if ckpt_names is not None:
             return self.infer_with_multiple_checkpoints(ckpt_names, domian_label)
+        postpro_name = cfg.get('post_process', None)                      # agent_seg.py:873-875 (after the ckpt_mode 3 return)
+        if self.postprocessor is None and postpro_name is not None:
+            self.postprocessor = self.postprocess_dict[postpro_name](cfg)
         # an injected inferer that overrides run() is called pass by pass, as the reference does
         batched_mc = isinstance(self.inferer, Inferer) and type(self.inferer).run is Inferer.run
         with torch.no_grad():
@@ -570,6 +585,9 @@ class SegmentationAgent(object):
             for a, b in zip(ls, lt):
                 conv[output == a] = b
             output = conv
+        if self.postprocessor is not None:                                    # agent_seg.py:1054-1056
+            for i in range(len(names)):
+                output[i] = self.postprocessor(output[i])
         root_dir = self.config['dataset']['root_dir']
         for i in range(len(names)):
             save_name = names[i].split('/')[-1] if ignore_dir else names[i].replace('/', '_')

@@ -644,3 +644,51 @@ def surface_min_dist(query_zyx, seed_zyx, spacing):
     call("fplx_surface_min_dist", ptr(q), q.shape[0], ptr(sd) if sd.shape[0] else 0, sd.shape[0], float(spacing[0]),
          float(spacing[1]), float(spacing[2]), ptr(out), stream())
     return out
+
+
+# ---------------------------------------------------------------- prediction post-processing (csrc/postprocess.hip)
+_CC_HEAD = 320          # ints in front of the per-voxel workspace (include/fplx.h FPLX_CC_LABEL_WS_BYTES / FPLX_KLC_WS_BYTES)
+
+
+def _cc_volume(seg):
+    require_gpu(seg)
+    if seg.dtype != torch.uint8 or seg.dim() not in (2, 3):
+        raise ValueError("fplx: connected components take a uint8 volume [D, H, W] or [H, W], got {0:} {1:}".format(
+            seg.dtype, tuple(seg.shape)))
+    s = seg.contiguous()
+    d, h, w = (1,) + tuple(s.shape) if s.dim() == 2 else tuple(s.shape)
+    return s, d, h, w
+
+
+def _cc_check(ws):
+    err = int(ws[0].item())
+    if err:
+        raise _lib.FplxError("fplx: connected components: a union-find loop reached its iteration cap (error word %d)" % err)
+
+
+def connected_components(seg, per_class=False):
+    """6-connected components of a uint8 device volume [D, H, W] ([H, W]: 4-connected) -> int32 labels of the same shape:
+    the C-order linear index of the component's first voxel, -1 for background.  per_class: neighbours join only when
+    their values are equal (every class labelled in one pass); otherwise whenever both are nonzero.  Synchronises once
+    (error word)."""
+    s, d, h, w = _cc_volume(seg)
+    labels = torch.empty(s.shape, dtype=torch.int32, device=s.device)
+    ws = torch.empty(_CC_HEAD, dtype=torch.int32, device=s.device)
+    call("fplx_cc_label", ptr(s), d, h, w, 1 if per_class else 0, ptr(labels), ptr(ws), ws.numel() * 4, stream())
+    _cc_check(ws)
+    return labels
+
+
+def keep_largest_component(seg, mode=1):
+    """PostKeepLargestComponent on a uint8 device volume [D, H, W] or [H, W]: mode 1 keeps the largest component of the
+    foreground, mode 2 the largest component of every foreground class; every component of the largest size is kept.
+    Synchronises once (error word)."""
+    if mode not in (1, 2):
+        raise ValueError("fplx: keep_largest_component mode must be 1 or 2, got {0!r}".format(mode))
+    s, d, h, w = _cc_volume(seg)
+    out = torch.empty_like(s)
+    ws = torch.empty(_CC_HEAD + 2 * s.numel(), dtype=torch.int32, device=s.device)
+    call("fplx_keep_largest_component", ptr(s), d, h, w, 1 if mode == 2 else 0, ptr(out), ptr(ws), ws.numel() * 4,
+         stream())
+    _cc_check(ws)
+    return out

@@ -498,6 +498,29 @@ int fplx_surface_edge_points(const unsigned char* img, int d, int h, int w, unsi
 int fplx_surface_min_dist(const int* query_zyx, int64_t nq, const int* seed_zyx, int64_t ns, float sz, float sy, float sx,
                           float* out, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ prediction post-processing
+ * Connected components of a uint8 volume seg [d][h][w] (d = 1: the 2D form), d * h * w < 2^31, under the 6-face
+ * connectivity of scipy.ndimage.generate_binary_structure(3, 1) (4 neighbours in 2D).  Two neighbours join when
+ * per_class == 0: both values are nonzero; per_class != 0: both values are equal and nonzero (every class in one pass).
+ *  fplx_cc_label: labels int32 [d][h][w] = the C-order linear index of the first voxel of the voxel's component (canonical
+ *                 labels), -1 for background.  Replaces scipy.ndimage.label in get_largest_k_components
+ *                 (PyMIC/pymic/util/image_process.py:139-163).
+ *  fplx_keep_largest_component: out uint8 [d][h][w] = seg where the voxel's component has the largest size among the
+ *                 components of its class (per_class == 0: one class, all foreground), else 0; every component of the
+ *                 maximal size is kept.  PostKeepLargestComponent (PyMIC/pymic/util/post_process.py:19-49), called by
+ *                 save_outputs (net_run_dsbn/agent_seg.py:1052-1054) - mode 1: per_class = 0, mode 2: per_class = 1.
+ *  ws: int32 workspace of at least FPLX_CC_LABEL_WS_BYTES / FPLX_KLC_WS_BYTES(d * h * w) bytes; ws[0] is the error word: 0
+ *      after a good run, nonzero when a union-find loop reached its iteration cap (the result is then invalid) - the
+ *      caller reads it after the stream has run the launches.
+ * Both return FPLX_E_NULL / FPLX_E_BADSHAPE / FPLX_E_WORKSPACE before any launch for a missing pointer or workspace, a
+ * non-positive dimension, 2^31 voxels or more, or a workspace that is too small. */
+#define FPLX_CC_LABEL_WS_BYTES(voxels) ((size_t)320 * 4)
+#define FPLX_KLC_WS_BYTES(voxels) (((size_t)320 + 2 * (size_t)(voxels)) * 4)
+int fplx_cc_label(const uint8_t* seg, int d, int h, int w, int per_class, int* labels, int* ws, size_t ws_bytes,
+                  fplx_stream_t stream);
+int fplx_keep_largest_component(const uint8_t* seg, int d, int h, int w, int per_class, uint8_t* out, int* ws,
+                                size_t ws_bytes, fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
