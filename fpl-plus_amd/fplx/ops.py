@@ -2,6 +2,8 @@
 device memory, the current HIP stream and dtype tags.  Activations are 2-D views
 [voxels, ld] of NDHWC tensors; a column slice `buf[:, a:b]` is a channel slice.
 """
+import ctypes
+
 import torch
 from . import _lib
 from ._lib import F32, BF16, call
@@ -574,6 +576,25 @@ def crop_flip(x, crop_min, out_size, flip_mask=0):
     y = torch.empty((c,) + tuple(out_size), dtype=x.dtype, device=x.device)
     call("fplx_crop_flip", ptr(x), ptr(y), _elem_bytes(x), c, d, h, w, crop_min[0], crop_min[1], crop_min[2], out_size[0],
          out_size[1], out_size[2], int(flip_mask), stream())
+    return y
+
+
+def resample_affine(x, matrix, offset, out_size, order):
+    """y[c][o] = interp(x[c], matrix o + offset) for a [C,D,H,W] volume -> [C,*out_size]: scipy.ndimage's affine resampling
+    (mode='constant', cval=0) for order 0 (float32 or uint8) and order 1 (float32).  matrix (3x3) and offset (3) are host
+    numbers, taken as fp64."""
+    require_gpu(x)
+    if not (x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("fplx: resample_affine takes a contiguous [C,D,H,W] volume")
+    m = [float(v) for row in matrix for v in row]
+    t = [float(v) for v in offset]
+    if len(m) != 9 or len(t) != 3 or len(out_size) != 3:
+        raise ValueError("fplx: resample_affine takes a 3x3 matrix, a 3-vector offset and a 3D output size")
+    c, d, h, w = x.shape
+    od, oh, ow = (int(v) for v in out_size)
+    y = torch.empty((c, max(od, 0), max(oh, 0), max(ow, 0)), dtype=x.dtype, device=x.device)
+    call("fplx_resample_affine", ptr(x), ptr(y), _elem_bytes(x), int(order), c, d, h, w, od, oh, ow,
+         (ctypes.c_double * 9)(*m), (ctypes.c_double * 3)(*t), stream())
     return y
 
 

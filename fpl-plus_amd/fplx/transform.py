@@ -1,17 +1,20 @@
 """Training-sample transforms on the GPU, behind PyMIC's transform interface.
 
 Mirrors the classes FPL+'s configs name (config_dual/data_vs/vs_t1s_g.cfg:21-23:
-train_transform = [NormalizeWithMeanStd, Pad, RandomCrop, RandomFlip, LabelToProbability]):
+train_transform = [NormalizeWithMeanStd, Pad, RandomCrop, RandomFlip, LabelToProbability]) and the geometric augmentation
+a user of the reference adds first (RandomRotate, Rescale, RandomRescale: rotate.py, rescale.py):
 same class names, same lower-cased parameter keys (PyMIC/pymic/transform/*.py), same `__call__(sample) -> sample`
 contract and the same `<Name>_Param` json strings in the sample, so `TransformDict[name](params)` drops in for
 PyMIC/pymic/transform/trans_dict.py:42.  The difference is where the volumes live: `sample['image']` (float32
 [C,D,H,W]), `sample['label']` (uint8 [1,D,H,W]) and `sample['pixel_weight']` (float32 [1,D,H,W]) are device tensors
-and every gather / reduction is a HIP kernel (csrc/sample.hip).  The random decisions are drawn on the host from
-Python's `random` in exactly the reference's order, so a seeded run picks the same crops and flips as the reference.
+and every gather / reduction / interpolation is a HIP kernel (csrc/sample.hip, csrc/resample.hip).  The random decisions
+are drawn on the host from Python's `random` (RandomRotate: numpy's global generator) in exactly the reference's order,
+so a seeded run picks the same crops, flips, angles and ratios as the reference.
 """
 import json
 import math
 import random
+from fractions import Fraction
 
 import numpy as np
 
@@ -229,12 +232,198 @@ class LabelToProbability(AbstractTransform):
         return sample
 
 
+# ---- geometric augmentation: RandomRotate, Rescale, RandomRescale.  One hot path, ops.resample_affine (csrc/resample.hip),
+# which restates scipy.ndimage's affine resampling (mode='constant', cval=0, orders 0 and 1) operation for operation; the
+# host below builds the fp64 matrix and offset scipy.ndimage.rotate / zoom would build.  Like the reference's rotate.py and
+# rescale.py these three touch 'image', 'label' and 'pixel_weight' only ('image1' is left as it is).
+
+def _fma(a, b, c):
+    """a * b + c rounded once (exact rational arithmetic; a handful of calls per sample)"""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _cos_sin_deg(angle):
+    """cos and sin of an angle in degrees, exact (0, +-1) at the multiples of 90 degrees as scipy.special.cosdg / sindg are:
+    math.cos(math.radians(180)) is not -1 to the last bit of its partner, and a whole border of the volume falls outside"""
+    r = math.fmod(float(angle), 360.0)
+    if math.fmod(r, 90.0) == 0.0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(r // 90.0) % 4]
+    a = math.radians(float(angle))
+    return math.cos(a), math.sin(a)
+
+
+def _rotate_affine(shape, angle, axes):
+    """matrix and offset of scipy.ndimage.rotate(angle, axes, reshape=False) on a [D,H,W] volume: scipy sorts the two axes,
+    R = [[cos, sin], [-sin, cos]] in that order, offset = (n - 1) / 2 - R (n - 1) / 2.  scipy forms R (n - 1) / 2 with a BLAS
+    matrix-vector product, which on every FMA-capable x86 rounds row i as fma(R[i][0], v_0, R[i][1] * v_1): the same here,
+    since one ulp of the offset can move a voxel on the border."""
+    a, b = sorted(ax % 3 for ax in axes)
+    c, s = _cos_sin_deg(angle)
+    m = [[1.0 if i == j else 0.0 for j in range(3)] for i in range(3)]
+    m[a][a], m[a][b], m[b][a], m[b][b] = c, s, -s, c
+    va, vb = (shape[a] - 1) / 2.0, (shape[b] - 1) / 2.0
+    t = [0.0, 0.0, 0.0]
+    t[a] = va - _fma(c, va, s * vb)
+    t[b] = vb - _fma(-s, va, c * vb)
+    return m, t
+
+
+def _zoom(x, zoom, order):
+    """scipy.ndimage.zoom(x, [1] + zoom, order) of a [C,D,H,W] volume: extents int(round(n * zoom)) (Python's round), the
+    coordinate step (n - 1) / (out - 1) - not 1 / zoom - and 1.0 where out == 1, offset 0"""
+    shape = x.shape[1:]
+    out = [int(round(shape[i] * zoom[i])) for i in range(3)]
+    step = [(shape[i] - 1.0) / (out[i] - 1.0) if out[i] > 1 else 1.0 for i in range(3)]
+    m = [[step[i] if i == j else 0.0 for j in range(3)] for i in range(3)]
+    return ops.resample_affine(x, m, (0.0, 0.0, 0.0), out, order)
+
+
+def _order_for(t, order):
+    if order == 1 and t.dtype != torch.float32:
+        raise ValueError("fplx.transform: linear interpolation takes float32 volumes, got {0:}".format(t.dtype))
+    return order
+
+
+def _on_prediction(sample, fn):
+    """apply fn([M,D,H,W]) -> [M,D',H',W'] to sample['predict'] ([N,C,D,H,W], or a list of those)"""
+    def one(pred):
+        n, c = pred.shape[:2]
+        out = fn(pred.contiguous().view(n * c, *pred.shape[2:]))
+        return out.view(n, c, *out.shape[1:])
+
+    predict = sample['predict']
+    sample['predict'] = [one(q) for q in predict] if isinstance(predict, (tuple, list)) else one(predict)
+    return sample
+
+
+def _json_param(p):
+    return json.loads(p[0] if isinstance(p, (list, tuple)) else p)
+
+
+class RandomRotate(AbstractTransform):
+    """rotate.py:14-92.  One np.random.uniform draw per plane whose range is not None, in the order d (axes -1, -2),
+    h (-1, -3), w (-2, -3); every rotation is a resampling pass of its own, as in the reference (interpolating three times
+    is not interpolating once).  Image and pixel weight: order 1, label: order 0."""
+
+    def __init__(self, params):
+        super(RandomRotate, self).__init__(params)
+        self.angle_range_d = params['randomrotate_angle_range_d']
+        self.angle_range_h = params['randomrotate_angle_range_h']
+        self.angle_range_w = params['randomrotate_angle_range_w']
+        self.inverse = params.get('randomrotate_inverse', True)
+
+    @staticmethod
+    def _apply(x, transform_param_list, order):
+        _order_for(x, order)
+        for angle, axes in transform_param_list:
+            m, t = _rotate_affine(x.shape[1:], angle, axes)
+            x = ops.resample_affine(x, m, t, x.shape[1:], order)
+        return x
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        transform_param_list = []
+        for rng, axes in ((self.angle_range_d, (-1, -2)), (self.angle_range_h, (-1, -3)), (self.angle_range_w, (-2, -3))):
+            if rng is not None:
+                transform_param_list.append([np.random.uniform(rng[0], rng[1]), axes])
+        assert len(transform_param_list) > 0
+        sample['RandomRotate_Param'] = json.dumps(transform_param_list)
+        sample['image'] = self._apply(image, transform_param_list, 1)
+        if 'label' in sample and self.task == 'segmentation':
+            sample['label'] = self._apply(_check_volume(sample['label'], 'label'), transform_param_list, 0)
+        if 'pixel_weight' in sample and self.task == 'segmentation':
+            sample['pixel_weight'] = self._apply(_check_volume(sample['pixel_weight'], 'pixel_weight'),
+                                                 transform_param_list, 1)
+        return sample
+
+    def inverse_transform_for_prediction(self, sample):
+        transform_param_list = _json_param(sample['RandomRotate_Param'])
+        transform_param_list.reverse()
+        inverse = [[-angle, axes] for angle, axes in transform_param_list]
+        return _on_prediction(sample, lambda p: self._apply(p, inverse, 1))
+
+
+class _RescaleBase(AbstractTransform):
+    _name = None
+
+    def _forward(self, sample, zoom):
+        image = _check_volume(sample['image'], 'image')
+        sample[self._name + '_origin_shape'] = json.dumps(list(image.shape))
+        sample['image'] = _zoom(image, zoom, _order_for(image, 1))
+        if 'label' in sample and self.task == 'segmentation':
+            sample['label'] = _zoom(_check_volume(sample['label'], 'label'), zoom, 0)
+        if 'pixel_weight' in sample and self.task == 'segmentation':
+            weight = _check_volume(sample['pixel_weight'], 'pixel_weight')
+            sample['pixel_weight'] = _zoom(weight, zoom, _order_for(weight, 1))
+        return sample
+
+    def inverse_transform_for_prediction(self, sample):
+        origin_shape = _json_param(sample[self._name + '_origin_shape'])
+
+        def back(p):                                     # [N*C, D, H, W]
+            zoom = [(origin_shape[1:][i] + 0.0) / p.shape[1 + i] for i in range(3)]
+            return _zoom(p, zoom, _order_for(p, 1))
+
+        return _on_prediction(sample, back)
+
+
+class Rescale(_RescaleBase):
+    """rescale.py:14-79.  rescale_output_size: [D, H, W] (D None: keep the depth) or an int (the smallest edge is matched,
+    the aspect ratio kept).  The inverse zooms the prediction back to the recorded shape with order 1."""
+    _name = 'Rescale'
+
+    def __init__(self, params):
+        super(Rescale, self).__init__(params)
+        self.output_size = params['rescale_output_size']
+        self.inverse = params.get('rescale_inverse', True)
+        assert isinstance(self.output_size, (int, list, tuple))
+
+    def __call__(self, sample):
+        shape = _check_volume(sample['image'], 'image').shape
+        if isinstance(self.output_size, (list, tuple)):
+            output_size = list(self.output_size)
+            if output_size[0] is None:
+                output_size[0] = shape[1]
+            assert len(output_size) == 3
+        else:
+            min_edge = min(shape[1:])
+            output_size = [self.output_size * shape[i + 1] / min_edge for i in range(3)]
+        return self._forward(sample, [(output_size[i] + 0.0) / shape[1:][i] for i in range(3)])
+
+
+class RandomRescale(_RescaleBase):
+    """rescale.py:81-153: one random.random() per axis, ratio = lower + draw * (upper - lower)."""
+    _name = 'RandomRescale'
+
+    def __init__(self, params):
+        super(RandomRescale, self).__init__(params)
+        self.ratio0 = params['randomrescale_lower_bound']
+        self.ratio1 = params['randomrescale_upper_bound']
+        self.inverse = params.get('randomrescale_inverse', True)
+        assert isinstance(self.ratio0, (float, list, tuple))
+        assert isinstance(self.ratio1, (float, list, tuple))
+
+    def __call__(self, sample):
+        _check_volume(sample['image'], 'image')
+        if isinstance(self.ratio0, (list, tuple)):
+            assert len(self.ratio0) == 3
+            for i in range(3):
+                assert self.ratio0[i] <= self.ratio1[i]
+            zoom = [self.ratio0[i] + random.random() * (self.ratio1[i] - self.ratio0[i]) for i in range(3)]
+        else:
+            zoom = [self.ratio0 + random.random() * (self.ratio1 - self.ratio0) for i in range(3)]
+        return self._forward(sample, zoom)
+
+
 TransformDict = {
     'NormalizeWithMeanStd': NormalizeWithMeanStd,
     'Pad': Pad,
     'RandomCrop': RandomCrop,
     'RandomFlip': RandomFlip,
     'LabelToProbability': LabelToProbability,
+    'RandomRotate': RandomRotate,
+    'Rescale': Rescale,
+    'RandomRescale': RandomRescale,
 }
 
 

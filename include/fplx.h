@@ -452,6 +452,21 @@ int fplx_label_to_probability(const unsigned char* label, float* prob, int class
                               fplx_stream_t stream);
 int fplx_set_weight(float* pixel_weight, int64_t n, float image_weight, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ geometric augmentation: affine resampling
+ * RandomRotate / Rescale / RandomRescale (PyMIC/pymic/transform/rotate.py:14-92, rescale.py:14-153), which the reference
+ * runs as scipy.ndimage.rotate / scipy.ndimage.zoom on the host.  y[ch][o] = interp(x[ch], M o + t) for x [c][d][h][w]
+ * and y [c][od][oh][ow], o = (o_d, o_h, o_w), with scipy's semantics for mode='constant', cval=0:
+ *  coordinates fp64, c_i = ((o_0 M[i][0] + o_1 M[i][1]) + o_2 M[i][2]) + t_i (offset last, no fused multiply-add);
+ *  any c_i < 0 or c_i > n_i - 1 (or NaN) -> 0;  order 0: x[floor(c_i + 0.5)];  order 1: weights (1 - y, 1 - (1 - y)) with
+ *  y = c - floor(c), fp64 sum over the 8 neighbours of ((x * w_d) * w_h) * w_w, k_d outermost, one cast to fp32.
+ *  elem_bytes 4 (fp32, order 0 or 1) or 1 (uint8, order 0 only); matrix9 (row-major 3x3) and offset3 are HOST arrays of
+ *  doubles, read before the call returns and passed to the kernel by value; one launch covers all channels; x and y
+ *  must not overlap.
+ * Refused before any launch: FPLX_E_NULL for a missing pointer; FPLX_E_BADSHAPE for a non-positive extent, 2^31 elements
+ * or more on either side, or an order other than 0 / 1; FPLX_E_BADDTYPE for another element size or uint8 with order 1. */
+int fplx_resample_affine(const void* x, void* y, int elem_bytes, int order, int c, int d, int h, int w, int od, int oh,
+                         int ow, const double* matrix9, const double* offset3, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ Inferer: sliding window + flip TTA
  * PyMIC/pymic/net_run_dsbn/infer_func.py:50-112 (tiling, overlap averaging), 188-222 (tta_mode 1).
  * The tile grid is the Cartesian product of per-axis start lists (HOST arrays, at most 64 entries each, non-decreasing,
