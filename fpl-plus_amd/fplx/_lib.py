@@ -64,7 +64,7 @@ F32, BF16 = 0, 1
 
 _CT = {
     "int": ctypes.c_int, "float": ctypes.c_float, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
-    "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32, "fplx_stream_t": ctypes.c_void_p,
+    "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32, "double": ctypes.c_double, "fplx_stream_t": ctypes.c_void_p,
 }
 
 

@@ -3,7 +3,9 @@ device memory, the current HIP stream and dtype tags.  Activations are 2-D views
 [voxels, ld] of NDHWC tensors; a column slice `buf[:, a:b]` is a channel slice.
 """
 import ctypes
+import math
 
+import numpy as np
 import torch
 from . import _lib
 from ._lib import F32, BF16, call
@@ -555,6 +557,148 @@ def normalize_positive(x, noise, out=None, want_moments=False):
     got = torch.empty(2, dtype=torch.float32, device=x.device) if want_moments else None
     call("fplx_normalize_positive", ptr(x), ptr(noise), ptr(out), x.numel(), ptr(ws), nb, ptr(got), stream())
     return (out, got) if want_moments else out
+
+
+# ---- intensity transforms (csrc/intensity.hip): one channel volume per call, fp32, contiguous; out=x runs in place
+
+def _chan(x, *more):
+    require_gpu(x, *more)
+    if not (x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0):
+        raise ValueError("fplx: intensity ops take a non-empty contiguous float32 volume")
+    return x
+
+
+def _f32(v):
+    """a host number as the float32 numpy makes of it next to a float32 array (NumPy 2: Python scalars are weak)"""
+    return float(np.float32(v))
+
+
+def channel_minmax(x, lower=None, upper=None):
+    """-> device float32[4] = [min, max, min and max of x clipped to lower / upper (each optional)]; NaN propagates"""
+    _chan(x)
+    ws = torch.empty(4, dtype=torch.int32, device=x.device)
+    out = torch.empty(4, dtype=torch.float32, device=x.device)
+    call("fplx_channel_minmax", ptr(x), x.numel(), 0.0 if lower is None else _f32(lower), int(lower is not None),
+         0.0 if upper is None else _f32(upper), int(upper is not None), ptr(ws), 16, ptr(out), stream())
+    return out
+
+
+def select_kth(x, ranks):
+    """exact order statistics: device float32 [len(ranks), 2] = (s[k], s[min(k + 1, n - 1)]) of the sorted values, 1..4 ranks"""
+    _chan(x)
+    ranks = [int(k) for k in ranks]
+    nb = _lib.lib().fplx_select_ws_bytes()
+    ws = torch.empty(nb // 4, dtype=torch.int32, device=x.device)
+    out = torch.empty((len(ranks), 2), dtype=torch.float32, device=x.device)
+    call("fplx_select_kth", ptr(x), x.numel(), (ctypes.c_int64 * max(len(ranks), 1))(*ranks), len(ranks), ptr(out), ptr(ws),
+         nb, stream())
+    return out
+
+
+def percentile_index(n, q):
+    """where numpy.percentile(x, q) (method 'linear') looks in the sorted float32 array of n values -> (lo, g): the result
+    interpolates s[lo] and s[min(lo + 1, n - 1)] with the weight g.  numpy does this in FLOAT32 when the data are float32
+    and q is a Python number: quantile = float32(q) / float32(100), index v = float32(n - 1) * quantile, each
+    rounded to float32, lo = floor(v), g = v - lo; v >= n - 1 reads the last element twice (g = v + 1
+    then, which multiplies a zero difference).  For n beyond 2^24 / 100 the index itself is rounded: numpy's choice, kept."""
+    f = np.float32
+    qq = f(q) / f(100)
+    v = f(n - 1) * qq
+    if v >= f(n - 1):
+        return n - 1, v + f(1)
+    lo = f(np.floor(v))
+    return int(lo), v - lo
+
+
+def percentile_lerp(a, b, g):
+    """numpy's _lerp on float32 scalars: a + (b - a) g below g = 0.5, else b - (b - a) (1 - g)"""
+    a, b, g = np.float32(a), np.float32(b), np.float32(g)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = b - a
+        return a + d * g if g < 0.5 else b - d * (np.float32(1) - g)
+
+
+def percentiles(x, qs):
+    """numpy.percentile(x, q) for each q (at most 3): one selection on the device, one device->host copy of the order
+    statistics, numpy's interpolation on the host -> list of numpy.float32.  The largest element rides along: a NaN
+    anywhere in x sorts last and makes every percentile NaN, as in numpy."""
+    n = x.numel()
+    for q in qs:
+        if not 0 <= q <= 100:
+            raise ValueError("Percentiles must be in the range [0, 100]")
+    idx = [percentile_index(n, q) for q in qs]
+    s = select_kth(x, [lo for lo, _ in idx] + [n - 1]).cpu().numpy()
+    if np.isnan(s[-1, 0]):
+        return [np.float32(np.nan) for _ in qs]
+    return [percentile_lerp(s[j, 0], s[j, 1], g) for j, (_, g) in enumerate(idx)]
+
+
+def clip_affine(x, v0, v1, a, b, out=None):
+    """(clip(x, v0, v1) - a) / b with host float32 numbers"""
+    _chan(x)
+    out = torch.empty_like(x) if out is None else out
+    call("fplx_clip_affine", ptr(x), ptr(out), x.numel(), _f32(v0), _f32(v1), _f32(a), _f32(b), stream())
+    return out
+
+
+def clip_affine_dev(x, v0, v1, a, hi, out=None):
+    """(clip(x, v0, v1) - a) / (hi - a) with v0, v1, a, hi one-element float32 device tensors (no host synchronisation)"""
+    _chan(x, v0, v1, a, hi)
+    for t in (v0, v1, a, hi):
+        assert t.dtype == torch.float32 and t.numel() >= 1
+    out = torch.empty_like(x) if out is None else out
+    call("fplx_clip_affine_dev", ptr(x), ptr(out), x.numel(), ptr(v0), ptr(v1), ptr(a), ptr(hi), stream())
+    return out
+
+
+def threshold_replace(x, t_lower, r_lower, t_upper, r_upper, out=None):
+    """x < t_lower -> r_lower, then > t_upper -> r_upper; a threshold of None switches its side off"""
+    _chan(x)
+    out = torch.empty_like(x) if out is None else out
+    call("fplx_threshold_replace", ptr(x), ptr(out), x.numel(), 0.0 if t_lower is None else _f32(t_lower),
+         0.0 if t_lower is None else _f32(r_lower), int(t_lower is not None), 0.0 if t_upper is None else _f32(t_upper),
+         0.0 if t_upper is None else _f32(r_upper), int(t_upper is not None), stream())
+    return out
+
+
+def normalize_range(x, noise, lower=None, upper=None, out=None, want_moments=False):
+    """(x - mean) / std with the moments of the voxels lower < x < upper (each bound optional); noise elsewhere"""
+    _chan(x, noise)
+    assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == x.numel()
+    out = torch.empty_like(x) if out is None else out
+    nb = _lib.lib().fplx_normalize_ws_bytes()
+    ws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+    got = torch.empty(2, dtype=torch.float32, device=x.device) if want_moments else None
+    call("fplx_normalize_range", ptr(x), ptr(noise), ptr(out), x.numel(), 0.0 if lower is None else _f32(lower),
+         int(lower is not None), 0.0 if upper is None else _f32(upper), int(upper is not None), ptr(ws), nb, ptr(got), stream())
+    return (out, got) if want_moments else out
+
+
+def gamma_correct(x, vmin, vmax, gamma, out=None):
+    """float32(((x - vmin) / (vmax - vmin)) ** float32(gamma)) * (vmax - vmin) + vmin; vmin, vmax: device scalars"""
+    _chan(x, vmin, vmax)
+    out = torch.empty_like(x) if out is None else out
+    call("fplx_gamma", ptr(x), ptr(out), x.numel(), ptr(vmin), ptr(vmax), _f32(gamma), stream())
+    return out
+
+
+def add_noise_f64(x, noise, out=None):
+    """float32(double(x) + noise) for a float64 device volume of the same size"""
+    _chan(x, noise)
+    assert noise.dtype == torch.float64 and noise.is_contiguous() and noise.numel() == x.numel()
+    out = torch.empty_like(x) if out is None else out
+    call("fplx_add_noise_f64", ptr(x), ptr(noise), ptr(out), x.numel(), stream())
+    return out
+
+
+def add_noise_philox(x, seed, stream_id, mean, std, out=None, want_uniforms=False):
+    """Gaussian noise generated on the device (Philox4x32-10 + Box-Muller in fp64, see include/fplx.h)"""
+    _chan(x)
+    out = torch.empty_like(x) if out is None else out
+    u = torch.empty((x.numel(), 2), dtype=torch.float64, device=x.device) if want_uniforms else None
+    call("fplx_add_noise_philox", ptr(x), ptr(out), x.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+         float(mean), float(std), ptr(u), stream())
+    return (out, u) if want_uniforms else out
 
 
 def pad_reflect(x, lower, out_size):

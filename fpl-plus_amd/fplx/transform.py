@@ -2,7 +2,8 @@
 
 Mirrors the classes FPL+'s configs name (config_dual/data_vs/vs_t1s_g.cfg:21-23:
 train_transform = [NormalizeWithMeanStd, Pad, RandomCrop, RandomFlip, LabelToProbability]) and the geometric augmentation
-a user of the reference adds first (RandomRotate, Rescale, RandomRescale: rotate.py, rescale.py):
+a user of the reference adds first (RandomRotate, Rescale, RandomRescale: rotate.py, rescale.py) and the intensity family
+(min-max / percentile normalisation, thresholding, gamma correction, Gaussian noise: normalize.py, threshold.py, intensity.py):
 same class names, same lower-cased parameter keys (PyMIC/pymic/transform/*.py), same `__call__(sample) -> sample`
 contract and the same `<Name>_Param` json strings in the sample, so `TransformDict[name](params)` drops in for
 PyMIC/pymic/transform/trans_dict.py:42.  The difference is where the volumes live: `sample['image']` (float32
@@ -415,6 +416,204 @@ class RandomRescale(_RescaleBase):
         return self._forward(sample, zoom)
 
 
+# ---- intensity transforms: NormalizeWithMinMax, NormalizeWithPercentiles, ChannelWiseThreshold,
+# ChannelWiseThresholdWithNormalize, GammaCorrection, GaussianNoise, NormalizeWithMeanStd_dual (normalize.py, threshold.py,
+# intensity.py).  They touch sample['image'] only, channel by channel and in place, like the reference.  The kernels
+# (csrc/intensity.hip) restate numpy's float32 arithmetic under NumPy 2: a Python-float parameter next to a float32 array
+# takes part as float32, while two Python floats combine in double first (v1 - v0 of two given thresholds).
+
+def _entry(values, i):
+    return None if values is None else values[i]
+
+
+def _scalar(x, v):
+    return torch.full((1,), float(np.float32(v)), dtype=torch.float32, device=x.device)
+
+
+class NormalizeWithMeanStd_dual(NormalizeWithMeanStd):
+    """normalize.py:70-152: NormalizeWithMeanStd on 'image', then on 'image1', with the same parameter keys.  mean / std
+    are filled on first use and shared by both, as in the reference."""
+
+    def __call__(self, sample):
+        _check_volume(sample['image1'], 'image1')
+        sample = super(NormalizeWithMeanStd_dual, self).__call__(sample)
+        other = super(NormalizeWithMeanStd_dual, self).__call__({'image': sample['image1']})
+        sample['image1'] = other['image']
+        return sample
+
+
+class NormalizeWithMinMax(AbstractTransform):
+    """normalize.py:155-197: clip to [v0, v1] and map to [0, 1]; v0 / v1 are the channel's min / max unless a threshold is
+    given (per entry).  A constant channel gives 0 / 0 = NaN, as in the reference."""
+
+    def __init__(self, params):
+        super(NormalizeWithMinMax, self).__init__(params)
+        self.chns = params['normalizewithminmax_channels']
+        self.thred_lower = params['normalizewithminmax_threshold_lower']
+        self.thred_upper = params['normalizewithminmax_threshold_upper']
+        self.inverse = params.get('normalizewithminmax_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        chns = self.chns if self.chns is not None else range(image.shape[0])
+        for i, chn in enumerate(chns):
+            x = image[chn]
+            lo, hi = _entry(self.thred_lower, i), _entry(self.thred_upper, i)
+            if lo is not None and hi is not None:
+                ops.clip_affine(x, lo, hi, lo, hi - lo, out=x)            # hi - lo: two host numbers, rounded once
+                continue
+            mm = ops.channel_minmax(x)                                    # stays on the device: no synchronisation
+            v0 = mm[0:1] if lo is None else _scalar(x, lo)
+            v1 = mm[1:2] if hi is None else _scalar(x, hi)
+            ops.clip_affine_dev(x, v0, v1, v0, v1, out=x)
+        sample['image'] = image
+        return sample
+
+
+class NormalizeWithPercentiles(AbstractTransform):
+    """normalize.py:199-237: v0 / v1 = numpy.percentile(channel, q) - exact order statistics selected on the device,
+    numpy's linear interpolation between the two neighbours on the host - then clip and map to [0, 1]."""
+
+    def __init__(self, params):
+        super(NormalizeWithPercentiles, self).__init__(params)
+        self.chns = params['normalizewithpercentiles_channels']
+        self.percent_lower = params['normalizewithpercentiles_percentile_lower']
+        self.percent_upper = params['normalizewithpercentiles_percentile_upper']
+        self.inverse = params.get('normalizewithpercentiles_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        chns = self.chns if self.chns is not None else range(image.shape[0])
+        for chn in chns:
+            x = image[chn]
+            v0, v1 = ops.percentiles(x, [self.percent_lower, self.percent_upper])
+            with np.errstate(invalid="ignore", over="ignore"):
+                ops.clip_affine(x, v0, v1, v0, v1 - v0, out=x)            # numpy.float32 - numpy.float32
+        sample['image'] = image
+        return sample
+
+
+class ChannelWiseThreshold(AbstractTransform):
+    """threshold.py:14-63: values below the lower threshold, then values above the upper one, are replaced (by the
+    threshold itself unless a replacement is given); every list is indexed by the position in `channels`."""
+
+    def __init__(self, params):
+        super(ChannelWiseThreshold, self).__init__(params)
+        self.channels = params['channelwisethreshold_channels']
+        self.threshold_lower = params['channelwisethreshold_threshold_lower']
+        self.threshold_upper = params['channelwisethreshold_threshold_upper']
+        self.replace_lower = params['channelwisethreshold_replace_lower']
+        self.replace_upper = params['channelwisethreshold_replace_upper']
+        self.inverse = params.get('channelwisethreshold_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        channels = range(image.shape[0]) if self.channels is None else self.channels
+        for i, chn in enumerate(channels):
+            t_lower, t_upper = _entry(self.threshold_lower, i), _entry(self.threshold_upper, i)
+            r_lower, r_upper = t_lower, t_upper
+            if t_lower is not None and _entry(self.replace_lower, i) is not None:
+                r_lower = self.replace_lower[i]
+            if t_upper is not None and _entry(self.replace_upper, i) is not None:
+                r_upper = self.replace_upper[i]
+            if t_lower is not None or t_upper is not None:
+                ops.threshold_replace(image[chn], t_lower, r_lower, t_upper, r_upper, out=image[chn])
+        sample['image'] = image
+        return sample
+
+
+class ChannelWiseThresholdWithNormalize(AbstractTransform):
+    """threshold.py:65-132.  The thresholds are indexed by the CHANNEL NUMBER, not by the position in `channels` - the
+    reference's indexing, kept.  mean_std_mode: moments of the voxels strictly inside (v0, v1), the others replaced by a
+    numpy.random.normal(0, 1) draw made on the host for the whole channel.  Otherwise: clip and divide by (max - min),
+    where min is v0 or the channel's min and max is the channel's max AFTER clipping."""
+
+    def __init__(self, params):
+        super(ChannelWiseThresholdWithNormalize, self).__init__(params)
+        self.channels = params['channelwisethresholdwithnormalize_channels']
+        self.threshold_lower = params['channelwisethresholdwithnormalize_threshold_lower']
+        self.threshold_upper = params['channelwisethresholdwithnormalize_threshold_upper']
+        self.mean_std_mode = params['channelwisethresholdwithnormalize_mean_std_mode']
+        self.inverse = params.get('channelwisethresholdwithnormalize_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        channels = range(image.shape[0]) if self.channels is None else self.channels
+        for chn in channels:
+            x = image[chn]
+            v0, v1 = self.threshold_lower[chn], self.threshold_upper[chn]
+            if self.mean_std_mode == True:                                # noqa: E712 (the reference's test)
+                noise = torch.from_numpy(np.random.normal(0, 1, size=tuple(x.shape)).astype(np.float32)).to(x.device)
+                ops.normalize_range(x, noise, v0, v1, out=x)
+                continue
+            mm = ops.channel_minmax(x, v0, v1)
+            lo = mm[0:1] if v0 is None else _scalar(x, v0)
+            hi = mm[1:2] if v1 is None else _scalar(x, v1)                # clipping at the channel's own max is no clipping
+            ops.clip_affine_dev(x, lo, hi, lo, mm[3:4], out=x)
+        sample['image'] = image
+        return sample
+
+
+class GammaCorrection(AbstractTransform):
+    """intensity.py:14-51.  Draw order: numpy.random.uniform() for the probability gate, then one random.random() per
+    listed channel.  The power is the correctly rounded one; numpy's float32 power is within 1 ulp of it."""
+
+    def __init__(self, params):
+        super(GammaCorrection, self).__init__(params)
+        self.channels = params['gammacorrection_channels']
+        self.gamma_min = params['gammacorrection_gamma_min']
+        self.gamma_max = params['gammacorrection_gamma_max']
+        self.prob = params.get('gammacorrection_probability', 0.5)
+        self.inverse = params.get('gammacorrection_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        if np.random.uniform() > self.prob:
+            return sample
+        self.last_gammas = []
+        for chn in self.channels:
+            gamma_c = random.random() * (self.gamma_max - self.gamma_min) + self.gamma_min
+            self.last_gammas.append(gamma_c)
+            mm = ops.channel_minmax(image[chn])
+            ops.gamma_correct(image[chn], mm[0:1], mm[1:2], gamma_c, out=image[chn])
+        sample['image'] = image
+        return sample
+
+
+class GaussianNoise(AbstractTransform):
+    """intensity.py:53-86.  Draw order: numpy.random.uniform() for the gate, then numpy.random.normal(mean, std, shape) per
+    listed channel - drawn on the host in float64 and uploaded, so that a seeded run adds the reference's noise.
+    `gaussiannoise_device_rng` (fplx only, default False; no reference counterpart, no parity with numpy's generator): the
+    noise is generated on the device from Philox4x32-10 keyed by one random.getrandbits(64) draw per firing call and the
+    channel number, and never exists on the host."""
+
+    def __init__(self, params):
+        super(GaussianNoise, self).__init__(params)
+        self.channels = params['gaussiannoise_channels']
+        self.mean = params['gaussiannoise_mean']
+        self.std = params['gaussiannoise_std']
+        self.prob = params.get('gaussiannoise_probability', 0.5)
+        self.inverse = params.get('gaussiannoise_inverse', False)
+        self.device_rng = params.get('gaussiannoise_device_rng', False)
+        self.last_seed = None
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        if np.random.uniform() > self.prob:
+            return sample
+        if self.device_rng:
+            self.last_seed = random.getrandbits(64)
+        for chn in self.channels:
+            x = image[chn]
+            if self.device_rng:
+                ops.add_noise_philox(x, self.last_seed, chn, self.mean, self.std, out=x)
+            else:
+                noise = torch.from_numpy(np.random.normal(self.mean, self.std, tuple(x.shape))).to(x.device)
+                ops.add_noise_f64(x, noise, out=x)
+        sample['image'] = image
+        return sample
+
+
 TransformDict = {
     'NormalizeWithMeanStd': NormalizeWithMeanStd,
     'Pad': Pad,
@@ -424,6 +623,13 @@ TransformDict = {
     'RandomRotate': RandomRotate,
     'Rescale': Rescale,
     'RandomRescale': RandomRescale,
+    'NormalizeWithMeanStd_dual': NormalizeWithMeanStd_dual,
+    'NormalizeWithMinMax': NormalizeWithMinMax,
+    'NormalizeWithPercentiles': NormalizeWithPercentiles,
+    'ChannelWiseThreshold': ChannelWiseThreshold,
+    'ChannelWiseThresholdWithNormalize': ChannelWiseThresholdWithNormalize,
+    'GammaCorrection': GammaCorrection,
+    'GaussianNoise': GaussianNoise,
 }
 
 

@@ -536,6 +536,49 @@ int fplx_cc_label(const uint8_t* seg, int d, int h, int w, int per_class, int* l
 int fplx_keep_largest_component(const uint8_t* seg, int d, int h, int w, int per_class, uint8_t* out, int* ws,
                                 size_t ws_bytes, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ intensity transforms
+ * NormalizeWithMinMax / NormalizeWithPercentiles (PyMIC/pymic/transform/normalize.py:155-237), ChannelWiseThreshold /
+ * ChannelWiseThresholdWithNormalize (threshold.py:14-132), GammaCorrection / GaussianNoise (intensity.py:14-86) on ONE channel
+ * volume x of n fp32 voxels, 0 < n < 2^31; y may alias x in every element pass.  All fp32 arithmetic is numpy's on a float32
+ * array under NumPy 2, operation for operation and without fused multiply-add; comparisons are written as numpy's masks
+ * (x < v0 -> v0), so a NaN voxel passes through a clip.
+ *  channel_minmax: out4 (device) = {min, max, min, max of the clipped data}, clipped = x < lo -> lo (if use_lo), then
+ *             x > hi -> hi (if use_hi).  Any NaN voxel makes all four NaN, as numpy's min / max do.  ws: 16 bytes.
+ *  select_kth: exact order statistics by radix selection (4 passes of 8 bits over an order-preserving integer key, no sort,
+ *             no host round trip, integer arithmetic only).  ranks: HOST array of 1..4 ranks k_j in [0, n), read before the
+ *             call returns; out (device) [nranks][2] = {s[k_j], s[min(k_j + 1, n - 1)]} of the ascending order s in which
+ *             NaNs come last, as in numpy's sort.  -0.0 and +0.0 are equal values and either may be returned for a tie
+ *             between them.  ws of fplx_select_ws_bytes() bytes.  A rank outside [0, n): FPLX_E_BADSHAPE before any launch.
+ *  clip_affine: y = (clip(x, v0, v1) - a) / b with clip as above; _dev reads v0, v1, a and hi from device memory and uses
+ *             b = *hi - *a (fp32), so a reduction feeds the pass without a host synchronisation.
+ *  threshold_replace: x < t_lo -> r_lo (if use_lo), then the result > t_hi -> r_hi (if use_hi).
+ *  normalize_range: ChannelWiseThresholdWithNormalize, mean_std_mode: float32 mean / population std over the voxels with
+ *             v0 < x < v1 (each bound optional; fp64 accumulation), y = (x - mean) / std there and noise[i] elsewhere (a NaN
+ *             voxel is elsewhere); an empty mask gives NaN moments and y = noise.  ws of fplx_normalize_ws_bytes() bytes;
+ *             out_mean_std may be NULL.
+ *  gamma:     d = *vmax - *vmin (device scalars); y = float32(pow(double((x - *vmin) / d), double(gamma))) * d + *vmin.
+ *  add_noise_f64: y = float32(double(x) + noise[i]) for the caller's fp64 noise volume (numpy.random.normal on the host).
+ *  add_noise_philox (no reference counterpart): element i takes words 2 (i & 1) and 2 (i & 1) + 1 of Philox4x32-10 with
+ *             counter (i >> 1, 0, stream_id, 0) and key (seed low, seed high); u = (word + 1) / 2^32 in (0, 1];
+ *             z = sqrt(-2 ln u1) cos(2 pi u2) in fp64; y = float32((double(x) + mean) + sigma * z).  out_uniforms (may be
+ *             NULL): fp64 [n][2] = {u1, u2}. */
+int fplx_channel_minmax(const float* x, int64_t n, float lo, int use_lo, float hi, int use_hi, void* ws, size_t ws_bytes,
+                        float* out4, fplx_stream_t stream);
+size_t fplx_select_ws_bytes(void);
+int fplx_select_kth(const float* x, int64_t n, const int64_t* ranks, int nranks, float* out, void* ws, size_t ws_bytes,
+                    fplx_stream_t stream);
+int fplx_clip_affine(const float* x, float* y, int64_t n, float v0, float v1, float a, float b, fplx_stream_t stream);
+int fplx_clip_affine_dev(const float* x, float* y, int64_t n, const float* v0, const float* v1, const float* a,
+                         const float* hi, fplx_stream_t stream);
+int fplx_threshold_replace(const float* x, float* y, int64_t n, float t_lo, float r_lo, int use_lo, float t_hi, float r_hi,
+                           int use_hi, fplx_stream_t stream);
+int fplx_normalize_range(const float* x, const float* noise, float* y, int64_t n, float v0, int use_v0, float v1, int use_v1,
+                         void* ws, size_t ws_bytes, float* out_mean_std, fplx_stream_t stream);
+int fplx_gamma(const float* x, float* y, int64_t n, const float* vmin, const float* vmax, float gamma, fplx_stream_t stream);
+int fplx_add_noise_f64(const float* x, const double* noise, float* y, int64_t n, fplx_stream_t stream);
+int fplx_add_noise_philox(const float* x, float* y, int64_t n, uint64_t seed, uint32_t stream_id, double mean, double sigma,
+                          double* out_uniforms, fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
