@@ -67,6 +67,14 @@ seg_loss_fwd_k(const float* __restrict__ logits, const float* __restrict__ label
         if (l[c] > best) { best = l[c]; am = c; }
     }
     softmax_argmax<C>(l, p, do_softmax != 0);
+    // the entropy regulariser takes softmax(outputs) whatever loss_softmax says (agent_seg.py:353): q = p with do_softmax
+    float q[MAXC];
+    if (do_softmax) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) q[c] = p[c];
+    } else {
+      softmax_argmax<C>(l, q, true);
+    }
     float ce = 0.f, ent = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -78,7 +86,7 @@ seg_loss_fwd_k(const float* __restrict__ logits, const float* __restrict__ label
       acc[6 * c + 4] += hc;
       acc[6 * c + 5] += y[c] * hc;
       ce -= y[c] * logf(p[c] * 0.999f + 5e-4f);
-      ent -= p[c] * log2f(p[c] + 1e-10f);
+      ent -= q[c] * log2f(q[c] + 1e-10f);
     }
     acc[6 * C + 0] += w * ce;
     acc[6 * C + 1] += w;
@@ -191,6 +199,10 @@ seg_loss_bwd_k(const float* __restrict__ logits, const float* __restrict__ label
     for (int c = 0; c < C; ++c) l[c] = lg[(int64_t)c * V + v];
     const float w = wp ? wp[v] : 1.f;
     softmax_argmax<C>(l, p, do_softmax != 0);
+    // without loss_softmax the Dice / CE gradients go to the outputs directly, the entropy term's still through ITS softmax
+    const bool ent_own = use_ent && !do_softmax;
+    float q[MAXC], ge[MAXC], dote = 0.f;
+    if (ent_own) softmax_argmax<C>(l, q, true);
     float dot = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -198,12 +210,20 @@ seg_loss_bwd_k(const float* __restrict__ logits, const float* __restrict__ label
       float gc = 0.f;
       if (use_dice) gc += w * fmaf(A[c], y, B[c]);
       if (use_ce) gc -= cce * w * y * 0.999f / (p[c] * 0.999f + 5e-4f);
-      if (use_ent) gc -= cent * (log2f(p[c] + 1e-10f) + p[c] * inv_ln2 / (p[c] + 1e-10f));
+      if (use_ent && do_softmax) gc -= cent * (log2f(p[c] + 1e-10f) + p[c] * inv_ln2 / (p[c] + 1e-10f));
+      if (ent_own) {
+        ge[c] = -cent * (log2f(q[c] + 1e-10f) + q[c] * inv_ln2 / (q[c] + 1e-10f));
+        dote = fmaf(ge[c], q[c], dote);
+      }
       g[c] = gc;
       dot = fmaf(gc, p[c], dot);
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) dl[(int64_t)c * V + v] = gs * (do_softmax ? p[c] * (g[c] - dot) : g[c]);
+    for (int c = 0; c < C; ++c) {
+      float d = do_softmax ? p[c] * (g[c] - dot) : g[c];
+      if (ent_own) d += q[c] * (ge[c] - dote);
+      dl[(int64_t)c * V + v] = gs * d;
+    }
   }
 }
 

@@ -354,8 +354,12 @@ int fplx_upsample2_bwd(const void* dy, int64_t ldy, void* dx, int64_t ldx, int n
  * Fused softmax + Dice (loss/seg/dice.py:20-57, util.py:85-107) + cross entropy
  * (loss/seg/ce.py:23-44) + per-sample image-weighted Dice (dice.py:106-128) + entropy
  * regulariser (net_run_dsbn/agent_seg.py:352-354) + hard-Dice train metric
- * (agent_seg.py:472-476).  logits / label: fp32 [N,C,D,H,W] contiguous (C <= 8);
+ * (agent_seg.py:472-476).  logits / label: fp32 [N,C,D,H,W] contiguous (1 <= C <= 8, N <= 64);
  * pixel_weight fp32 [N,1,D,H,W] or NULL.
+ *   softmax  1: Dice and CE take softmax(logits); 0: they take the outputs as they are (loss_softmax = False, the outputs are
+ *          probabilities).  The entropy regulariser applies softmax to the outputs in BOTH cases, as the reference does
+ *          (agent_seg.py:353 `outputs.softmax(1)`): with softmax = 0 its value and gradient still go through softmax(logits),
+ *          and the hard-Dice metric takes the first maximum of the raw outputs either way.
  *   part   fp32 workspace [N][rows][FPLX_LOSS_K(C)], rows = fplx_loss_rows(D*H*W) (partial rows + 5 spare rows that hold the
  *          per-sample sums and batch totals as (N + 1) x K doubles, 8-byte aligned: exactly N*rows*K floats are touched)
  *   cfg    host floats: w_dice, w_ce, w_dice_img (per-sample Dice x image_weight), w_entropy
@@ -406,7 +410,8 @@ int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n,
 
 /* ------------------------------------------------------------------ pseudo-label filter
  * FPL branch of SegmentationAgent.infer (net_run_dsbn/agent_seg.py:911-931) for one volume:
- * logits fp32 [T][C][V] (T MC/TTA passes).  Per voxel: softmax per pass (scipy.special.softmax,
+ * logits fp32 [T][C][V] (T MC/TTA passes; 1 <= T <= 16 and 2 <= C <= 4, anything else is refused with FPLX_E_BADSHAPE).
+ * Per voxel: softmax per pass (scipy.special.softmax,
  * fp32), hard label per pass (argmax, uint8 [T][V], may be NULL), population variance over T
  * summed over classes, mean_T p_1, u = -m*log(m+1e-6), boundary = #(u > thr).
  *   part  workspace fp32/int [rows][2] (rows = fplx_num_partials(V))
