@@ -112,6 +112,14 @@ __device__ __forceinline__ FplxTileRange fplx_xcd_tiles(int64_t ntiles, int on) 
   t.step = (gridDim.x - c + 7u) >> 3;
   return t;
 }
+// ---- host side: launch of a kernel with dynamic LDS.  The limit is declared to the runtime on EVERY such launch (a
+// per-function attribute; nothing is cached here), then the kernel is enqueued; errors are collected afterwards by
+// fplx_check_launch.  The arguments convert implicitly to the kernel's parameter types: a wrong one does not compile.
+template <typename... P, typename... A>
+inline void fplx_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  if (lds) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  kernel<<<grid, block, lds, st>>>(args...);
+}
 #endif
 // ---- tuning table (fplx_set_tuning / fplx_get_tuning, include/fplx.h): ONE process-wide table of named integer knobs
 // for A/B measurements - every default is the shipped configuration and no knob changes a result, only which kernel /

@@ -17,7 +17,7 @@
 //   * LDS image: voxel rows of 64 B, voxel index L = plane * 128 + row * 12 + col, 16-byte chunks XOR-swizzled with
 //     (L >> 2) & 3; the lane -> voxel map of an M-tile follows ds_read_b128's lane groups so that each group touches
 //     16 distinct 16-byte slots for every tap shift (rows 0, 2 in one group, rows 1, 3 in the other).
-#include "common.h"
+#include "internal.h"
 #include <type_traits>
 
 #ifdef FPLX_STAMP
@@ -747,50 +747,27 @@ extern "C" int fplx_brick_conv3d_fwd_act(const void* x, int64_t ldx, const void*
   }
   dim3 grid((unsigned)gx, gy, ksplit);
   float* part = ksplit > 1 ? partial : nullptr;
-#define LAUNCH_BRICK(STATS_, NTW_, TD_, WH_)                                                                         \
-  do {                                                                                                               \
-    using G_ = BKG<TD_, WH_, NTW_>;                                                                                  \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_brick_lw<STATS_, NTW_, TD_, WH_>,                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS);                                  \
-    conv_fwd_brick_lw<STATS_, NTW_, TD_, WH_><<<grid, 512, G_::LDS, st>>>(                                            \
-        (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, stats, part, bD, bH,  \
-        bW, xcd_on);                                                                                                 \
-  } while (0)
-  const bool st_ = stats && !part;
-#define LAUNCH_BRICK_ACT(NTW_, TD_, WH_)                                                                              \
-  do {                                                                                                               \
-    using G_ = BKG<TD_, WH_, NTW_>;                                                                                  \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_brick_lw<false, NTW_, TD_, WH_, true>,                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS);                                  \
-    conv_fwd_brick_lw<false, NTW_, TD_, WH_, true><<<grid, 512, G_::LDS, st>>>(                                       \
-        (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, nullptr, nullptr, bD,  \
-        bH, bW, xcd_on, slope);                                                                                      \
-  } while (0)
-#define LAUNCH_BRICK_ACT2(NTW_, TD_, WH_)                                                                             \
-  do {                                                                                                               \
-    using G_ = BKG<TD_, WH_, NTW_>;                                                                                  \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_brick_lw<false, NTW_, TD_, WH_, true, true>,                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS);                                  \
-    conv_fwd_brick_lw<false, NTW_, TD_, WH_, true, true><<<grid, 512, G_::LDS, st>>>(                                 \
-        (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, nullptr, nullptr, bD,  \
-        bH, bW, xcd_on, slope, (const bf16_t*)x1, nmod0);                                                            \
-  } while (0)
-  if (x1) {
-    if (geo == 1) LAUNCH_BRICK_ACT2(1, 5, 1);
-    else if (nt == 128) LAUNCH_BRICK_ACT2(2, 4, 2);
-    else LAUNCH_BRICK_ACT2(1, 4, 2);
+  // the forms: x1: activation write-out on a two-tensor input; slope without a Cin split: activation write-out (with a split
+  // the activation is the finish kernel's); else the plain kernel, with the statistics when it writes y itself
+  const bool cat2 = x1 != nullptr, act = cat2 || (slope && !part), st_ = stats && !part;
+  auto launch = [&](auto kernel, int lds) {
+    fplx_launch(kernel, grid, 512, lds, st, (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout,
+                act ? nullptr : stats, act ? nullptr : part, bD, bH, bW, xcd_on, act ? slope : nullptr,
+                cat2 ? (const bf16_t*)x1 : nullptr, cat2 ? nmod0 : 0);
+  };
+  // conv_fwd_brick_lw<STATS, NTW, TD, WH, ACT, CAT2> on BKG<TD, WH, NTW>: 5 x 4 x 8 bricks | 4 x 8 x 8 with 128 | 64 channels
+  if (cat2) {
+    if (geo == 1) launch(conv_fwd_brick_lw<false, 1, 5, 1, true, true>, BKG<5, 1, 1>::LDS);
+    else if (nt == 128) launch(conv_fwd_brick_lw<false, 2, 4, 2, true, true>, BKG<4, 2, 2>::LDS);
+    else launch(conv_fwd_brick_lw<false, 1, 4, 2, true, true>, BKG<4, 2, 1>::LDS);
+  } else if (act) {
+    if (geo == 1) launch(conv_fwd_brick_lw<false, 1, 5, 1, true>, BKG<5, 1, 1>::LDS);
+    else if (nt == 128) launch(conv_fwd_brick_lw<false, 2, 4, 2, true>, BKG<4, 2, 2>::LDS);
+    else launch(conv_fwd_brick_lw<false, 1, 4, 2, true>, BKG<4, 2, 1>::LDS);
   }
-  else if (slope && !part) {          // (with a Cin split the activation is the finish kernel's)
-    if (geo == 1) LAUNCH_BRICK_ACT(1, 5, 1);
-    else if (nt == 128) LAUNCH_BRICK_ACT(2, 4, 2);
-    else LAUNCH_BRICK_ACT(1, 4, 2);
-  }
-  else if (geo == 1) { if (st_) LAUNCH_BRICK(true, 1, 5, 1); else LAUNCH_BRICK(false, 1, 5, 1); }
-  else if (nt == 128) { if (st_) LAUNCH_BRICK(true, 2, 4, 2); else LAUNCH_BRICK(false, 2, 4, 2); }
-  else { if (st_) LAUNCH_BRICK(true, 1, 4, 2); else LAUNCH_BRICK(false, 1, 4, 2); }
-#undef LAUNCH_BRICK_ACT2
-#undef LAUNCH_BRICK_ACT
-#undef LAUNCH_BRICK
+  else if (geo == 1) { if (st_) launch(conv_fwd_brick_lw<true, 1, 5, 1>, BKG<5, 1, 1>::LDS); else launch(conv_fwd_brick_lw<false, 1, 5, 1>, BKG<5, 1, 1>::LDS); }
+  else if (nt == 128) { if (st_) launch(conv_fwd_brick_lw<true, 2, 4, 2>, BKG<4, 2, 2>::LDS); else launch(conv_fwd_brick_lw<false, 2, 4, 2>, BKG<4, 2, 2>::LDS); }
+  else { if (st_) launch(conv_fwd_brick_lw<true, 1, 4, 2>, BKG<4, 2, 1>::LDS); else launch(conv_fwd_brick_lw<false, 1, 4, 2>, BKG<4, 2, 1>::LDS); }
   const int rc = fplx_check_launch("brick_conv3d_fwd");
   return rc < 0 ? rc : 1;
 }

@@ -3,7 +3,7 @@
 //   out_conv  Conv3d(C0 -> class_num, 1x3x3) writing fp32 NCDHW logits            (unet2d5_dsbn.py:293-294,307)
 // They still run on the matrix cores (padding K / N to the 32x32x16 tile) because the VALU
 // formulation is ~10x over the HBM time; with MFMA all five kernels sit at the memory roof.
-#include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 
 namespace {

@@ -2,7 +2,7 @@
 // They serve (a) the fp32 parity mode, (b) layers the MFMA kernels do not cover (odd channel
 // counts), (c) the in-GPU cross-check of the MFMA kernels.  The bf16 hot path of the 3x3x3
 // convolutions is in conv_mfma.hip.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -552,77 +552,6 @@ inline int wgrad_chunks(int64_t V) {
 
 }  // namespace
 
-// MFMA fast paths (conv_mfma.hip); return 1 if they handled the call, 0 if not applicable, <0 on error
-extern "C" int fplx_mfma_conv3d_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                    int n, int d, int h, int w, int cin, int cout, float* stats, void* ws,
-                                    size_t ws_bytes, hipStream_t st);
-extern "C" size_t fplx_mfma_conv3d_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_mfma_conv3d_act_ok(int n, int d, int h, int w, int cin, int cout, int mid);
-extern "C" int fplx_mfma_conv3d_act_cat2_ok(int n, int d, int h, int w, int cin, int cout, int mid);
-extern "C" int fplx_mfma_conv3d_fwd_act_cat2(const void* x0, const void* x1, int64_t ldx, const void* wp, const float* bias,
-                                             const float* slope, void* y, int64_t ldy, int n, int d, int h, int w, int cin,
-                                             int cout, int nmod0, hipStream_t st);
-extern "C" int fplx_mfma_conv3d_fwd_act(const void* x, int64_t ldx, const void* wp, const float* bias, const float* slope, void* y,
-                                        int64_t ldy, int n, int d, int h, int w, int cin, int cout, void* ws, size_t ws_bytes,
-                                        int mid, hipStream_t st);
-extern "C" int fplx_march_conv3d_fwd_act(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                         int n, int d, int h, int w, int cin, int cout, float* stats, hipStream_t st,
-                                         const void* x1, void* y1, int twod, const float* slope, int nmod0);
-extern "C" int fplx_mfma_conv3d_plan(int n, int d, int h, int w, int cin, int cout, int mid, int* kernel, int* geo, int* ksplit);
-extern "C" int fplx_mfma_conv3d_stats_rows(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_edge_stem_rows(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_edge_stem_fwd(const float* x, const void* wf, const float* bias, void* y, int64_t ldy, int n, int d,
-                                  int h, int w, int cin, int cout, float* stats, hipStream_t st);
-extern "C" size_t fplx_edge_stem_wgrad_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_edge_stem_wgrad_bn(const float* x, const void* dy, int64_t ldy, float* dw, int n, int d, int h, int w,
-                                       int cin, int cout, void* ws, hipStream_t st, const void* y, int64_t ldyy, const float* mean,
-                                       const float* rstd, const float* scale, const float* shift, const float* slope,
-                                       const float* coef);
-extern "C" int fplx_edge_stem_wgrad(const float* x, const void* dy, int64_t ldy, float* dw, int n, int d, int h, int w,
-                                    int cin, int cout, void* ws, hipStream_t st);
-extern "C" int fplx_edge_outconv_fwd(const void* x, int64_t ldx, const float* wf, const float* bias, float* out, int n,
-                                     int d, int h, int w, int cin, int ncls, hipStream_t st);
-extern "C" int fplx_edge_outconv_bn_ok(int n, int d, int h, int w, int c0, int ncls);
-extern "C" int fplx_edge_outconv_bn_rows(int n, int d, int h, int w, int ncls);
-extern "C" int fplx_edge_outconv_fwd_bn(const void* y, int64_t ldy, const float* scale, const float* shift, const float* slope,
-                                        void* a, int64_t lda, const float* wf, const float* bias, float* out, int n, int d,
-                                        int h, int w, int c0, int ncls, hipStream_t st);
-extern "C" int fplx_edge_outconv_dgrad_bn(int mode, const float* dl, const void* wb, const void* y, int64_t ldy,
-                                          const float* mean, const float* rstd, const float* scale, const float* shift,
-                                          const float* slope, const float* coef, float* part, void* dy, int64_t lddy, int n,
-                                          int d, int h, int w, int c0, int ncls, hipStream_t st);
-extern "C" int fplx_edge_outconv_dgrad(const float* dl, const void* wb, void* dx, int64_t ldx, int n, int d, int h, int w,
-                                       int c0, int ncls, hipStream_t st);
-extern "C" size_t fplx_edge_outconv_wgrad_ws_bytes(int n, int d, int h, int w, int c0, int ncls);
-extern "C" size_t fplx_edge_outconv_wgrad_bn_ws_bytes(int n, int d, int h, int w, int c0, int ncls);
-extern "C" int fplx_edge_outconv_wgrad_bn(const void* y, int64_t ldy, const float* scale, const float* shift, const float* slope,
-                                          const float* dl, float* dw, float* db, int n, int d, int h, int w, int c0, int ncls,
-                                          void* ws, hipStream_t st);
-extern "C" int fplx_edge_outconv_wgrad(const void* x, int64_t ldx, const float* dl, float* dw, int n, int d, int h, int w,
-                                       int c0, int ncls, void* ws, hipStream_t st);
-extern "C" int fplx_mfma_deconv2_fwd(const void* x, int64_t ldx, const void* wf, const float* bias, void* y, int64_t ldy,
-                                     int n, int d, int h, int w, int cin, int cout, int sd, hipStream_t st);
-extern "C" int fplx_mfma_deconv2_dgrad(const void* dy, int64_t ldy, const void* wb, void* dx, int64_t ldx, int n, int d,
-                                       int h, int w, int cin, int cout, int sd, hipStream_t st);
-extern "C" size_t fplx_mfma_deconv2_wgrad_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_mfma_deconv2_wgrad(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, float* db,
-                                       int n, int d, int h, int w, int cin, int cout, void* ws, size_t ws_bytes,
-                                       int sd, hipStream_t st);
-extern "C" size_t fplx_mfma_conv3d_wgrad_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_mfma_conv3d_mid_stats_rows(int n, int d, int h, int w, int cin, int cout);
-extern "C" size_t fplx_mfma_conv3d_mid_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_mfma_conv3d_mid_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y,
-                                        int64_t ldy, int n, int d, int h, int w, int cin, int cout, float* stats, void* ws,
-                                        size_t ws_bytes, hipStream_t st);
-extern "C" int fplx_mfma_conv3d_wgrad(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, int n, int d,
-                                      int h, int w, int cin, int cout, void* ws, size_t ws_bytes, hipStream_t st,
-                                      const void* x1, int mid);
-extern "C" int fplx_mfma_conv3d_wgrad_cit(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_march_ok(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_march_conv3d_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                     int n, int d, int h, int w, int cin, int cout, float* stats, hipStream_t st,
-                                     const void* x1, void* y1, int twod);
-
 extern "C" {
 
 int fplx_version(void) { return 1; }
@@ -857,7 +786,7 @@ static bool is_planar(int64_t sn, int64_t sd, int64_t sh, int64_t sw, int64_t sc
 
 int fplx_conv3d_stats_rows(int n, int d, int h, int w, int cin, int cout, int kd, int kh, int kw, int x_dt, int y_dt) {
   if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3) {
-    int r = fplx_mfma_conv3d_stats_rows(n, d, h, w, cin, cout);
+    int r = fplx_mfma_conv3d_stats_rows(n, d, h, w, cin, cout, 0);
     if (r > 0) return r;
   }
   if (x_dt == FPLX_F32 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3) {   // stem: fp32 network input
@@ -870,7 +799,7 @@ int fplx_conv3d_stats_rows(int n, int d, int h, int w, int cin, int cout, int kd
 
 size_t fplx_conv3d_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout, int kd, int kh, int kw, int x_dt, int y_dt) {
   if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3)
-    return fplx_mfma_conv3d_fwd_ws_bytes(n, d, h, w, cin, cout);
+    return fplx_mfma_conv3d_fwd_ws_bytes(n, d, h, w, cin, cout, 0);
   return 0;
 }
 
@@ -901,9 +830,9 @@ int fplx_conv3d_fwd(const void* x, int x_dt, int64_t sn, int64_t sd, int64_t sh,
   FPLX_REQUIRE((kd & 1) && (kh & 1) && (kw & 1) && kd <= 3 && kh <= 3 && kw <= 3, FPLX_E_BADSHAPE,
                "conv3d_fwd: kernel %dx%dx%d unsupported (odd sizes <= 3)", kd, kh, kw);
   hipStream_t st = (hipStream_t)stream;
-  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3 && sc == 1 && yc == 1 &&
-      sh == sw * w && sd == sh * h && sn == sd * d && yh == yw * w && yd == yh * h && yn == yd * d) {
-    int r = fplx_mfma_conv3d_fwd(x, sw, wp, bias, y, yw, n, d, h, w, cin, cout, stats, ws, ws_bytes, st);
+  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3 && is_cl(sn, sd, sh, sw, sc, d, h, w) &&
+      is_cl(yn, yd, yh, yw, yc, d, h, w)) {
+    int r = fplx_mfma_conv3d_fwd(x, sw, wp, bias, y, yw, n, d, h, w, cin, cout, stats, ws, ws_bytes, 0, st);
     if (r != 0) return r < 0 ? r : FPLX_OK;
   }
   if (x_dt == FPLX_F32 && y_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3 &&
@@ -945,14 +874,14 @@ int fplx_conv3d_fwd(const void* x, int x_dt, int64_t sn, int64_t sd, int64_t sh,
  * implicit-GEMM kernel skip the 18 dead taps. */
 int fplx_conv2d_stats_rows(int n, int d, int h, int w, int cin, int cout, int x_dt, int y_dt) {
   if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16) {
-    int r = fplx_mfma_conv3d_mid_stats_rows(n, d, h, w, cin, cout);
+    int r = fplx_mfma_conv3d_stats_rows(n, d, h, w, cin, cout, 1);
     if (r > 0) return r;
   }
   return fplx_conv3d_stats_rows(n, d, h, w, cin, cout, 3, 3, 3, x_dt, y_dt);
 }
 
 size_t fplx_conv2d_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout, int x_dt, int y_dt) {
-  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16) return fplx_mfma_conv3d_mid_fwd_ws_bytes(n, d, h, w, cin, cout);
+  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16) return fplx_mfma_conv3d_fwd_ws_bytes(n, d, h, w, cin, cout, 1);
   return 0;
 }
 
@@ -962,9 +891,8 @@ int fplx_conv2d_fwd(const void* x, int x_dt, int64_t sn, int64_t sd, int64_t sh,
                     fplx_stream_t stream) {
   FPLX_REQUIRE(x && wp && y, FPLX_E_NULL, "conv2d_fwd: null pointer");
   FPLX_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, FPLX_E_BADSHAPE, "conv2d_fwd: bad shape");
-  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && sc == 1 && yc == 1 && sh == sw * w && sd == sh * h && sn == sd * d &&
-      yh == yw * w && yd == yh * h && yn == yd * d) {
-    int r = fplx_mfma_conv3d_mid_fwd(x, sw, wp, bias, y, yw, n, d, h, w, cin, cout, stats, ws, ws_bytes, (hipStream_t)stream);
+  if (x_dt == FPLX_BF16 && y_dt == FPLX_BF16 && is_cl(sn, sd, sh, sw, sc, d, h, w) && is_cl(yn, yd, yh, yw, yc, d, h, w)) {
+    int r = fplx_mfma_conv3d_fwd(x, sw, wp, bias, y, yw, n, d, h, w, cin, cout, stats, ws, ws_bytes, 1, (hipStream_t)stream);
     if (r != 0) return r < 0 ? r : FPLX_OK;
   }
   // not on the MFMA path (dtype / layout / alignment): all 27 taps through fplx_conv3d_fwd - the same result; the
@@ -1184,8 +1112,8 @@ int fplx_conv3d_wgrad(const void* x, int x_dt, int64_t sn, int64_t sd, int64_t s
   Strides xs{sn, sd, sh, sw, sc}, ys{yn, yd, yh, yw, yc};
   bool done = false;
   size_t used = (size_t)chunks * taps * cout * cin * sizeof(float);
-  if (x_dt == FPLX_BF16 && dy_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3 && sc == 1 && yc == 1 &&
-      sh == sw * w && sd == sh * h && sn == sd * d && yh == yw * w && yd == yh * h && yn == yd * d) {
+  if (x_dt == FPLX_BF16 && dy_dt == FPLX_BF16 && kd == 3 && kh == 3 && kw == 3 && is_cl(sn, sd, sh, sw, sc, d, h, w) &&
+      is_cl(yn, yd, yh, yw, yc, d, h, w)) {
     const size_t m = fplx_mfma_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout);
     if (m > 0) {
       int r = fplx_mfma_conv3d_wgrad(x, sw, dy, yw, dw, n, d, h, w, cin, cout, ws, m, st, nullptr, 0);
@@ -1249,8 +1177,7 @@ int fplx_conv2d_wgrad(const void* x, int x_dt, int64_t sn, int64_t sd, int64_t s
                "conv2d_wgrad: workspace %zu < %zu", ws_bytes, fplx_conv2d_wgrad_ws_bytes(n, d, h, w, cin, cout));
   hipStream_t st = (hipStream_t)stream;
   const size_t w3 = fplx_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout, 3, 3, 3);
-  if (x_dt == FPLX_BF16 && dy_dt == FPLX_BF16 && sc == 1 && yc == 1 && sh == sw * w && sd == sh * h && sn == sd * d &&
-      yh == yw * w && yd == yh * h && yn == yd * d) {
+  if (x_dt == FPLX_BF16 && dy_dt == FPLX_BF16 && is_cl(sn, sd, sh, sw, sc, d, h, w) && is_cl(yn, yd, yh, yw, yc, d, h, w)) {
     const size_t m = fplx_mfma_conv3d_wgrad_ws_bytes(n, d, h, w, cin, cout);
     if (m > 0) {
       int r = fplx_mfma_conv3d_wgrad(x, sw, dy, yw, dw, n, d, h, w, cin, cout, ws, m, st, nullptr, 1);

@@ -19,7 +19,7 @@
 // Replaces (for these shapes) nn.Conv3d forward and, with the mirrored pack, its data gradient -
 // reference PyMIC/pymic/net/net3d/unet2d5_dsbn.py:54-55,75,79 (ConvolutionLayer / ConvBlockND), and the
 // torch.cat of unet2d5_dsbn.py:182 when the input / output is given as two tensors (x1 / y1).
-#include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1677,54 +1677,29 @@ extern "C" int fplx_march_conv3d_fwd_act(const void* x, int64_t ldx, const void*
   dim3 grid(c.nblk, cout / 32);
   if (cin >= 64) {
     if (y1 || (cin == 128 && x1)) return 0;
-#define LAUNCH_M64Q(G_, TWOD_, NQ_)                                                                                 \
-  do {                                                                                                              \
-    if (slope) {                                                                                                    \
-      (void)hipFuncSetAttribute((const void*)conv_fwd_march64<G_, TWOD_, NQ_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-      conv_fwd_march64<G_, TWOD_, NQ_, true><<<grid, G_::THREADS, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, \
-                                                                         (bf16_t*)y, ldy, n, d, h, w, cout, nullptr, c.tilesH, \
-                                                                         c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on(), slope, nmod0); \
-    } else {                                                                                                        \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march64<G_, TWOD_, NQ_>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-    conv_fwd_march64<G_, TWOD_, NQ_><<<grid, G_::THREADS, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, \
-                                                                         (bf16_t*)y, ldy, n, d, h, w, cout, stats, c.tilesH, \
-                                                                         c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on()); \
-    }                                                                                                               \
-  } while (0)
     // loader-wave form (knob march64_lw, default on): the Conv2d-per-slice forms only (TWOD: one live accumulator role, 135-200
     // registers: -21..-28 % per launch, profiles/r05_kernel_ab.txt).  Needs a depth slice below 1 GiB (32-bit buffer offsets, the
     // out-of-range marker).  The 3D forms stay on conv_fwd_march64: their eight accumulator tiles + the rotation's copies do not
     // fit 256 registers (57-78 spilled registers inside the MFMA loop: +23 %, profiles/r05_kernel_ab.txt section 4) - that
     // instantiation was removed in round 6
     const bool lw64 = twod && fplx_knob(FPLX_K_MARCH64_LW) != 0 && (int64_t)h * w * ldx * 2 < ((int64_t)1 << 30);
-#define LAUNCH_M64LW(G_, NQ_)                                                                                       \
+    auto launch = [&](auto kernel, int threads, int lds) {      // slope: the ACT instantiations, no statistics
+      fplx_launch(kernel, grid, threads, lds, st, (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cout,
+                  slope ? nullptr : stats, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on(), slope,
+                  slope ? nmod0 : 0);
+    };
+    // <G, TWOD, NQ, ACT>: NQ = 4 is the streamed-weight form for Cin = 128
+#define M64_KERNEL(K_, G_, TWOD_)                                                                                    \
+  (cin == 128 ? (slope ? K_<G_, TWOD_, 4, true> : K_<G_, TWOD_, 4>) : (slope ? K_<G_, TWOD_, 2, true> : K_<G_, TWOD_, 2>))
+#define M64_FOOTPRINT(G_)                                                                                            \
   do {                                                                                                              \
-    if (slope) {                                                                                                    \
-      (void)hipFuncSetAttribute((const void*)conv_fwd_march64_lw<G_, true, NQ_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-      conv_fwd_march64_lw<G_, true, NQ_, true><<<grid, 512, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, \
-                                                                         (bf16_t*)y, ldy, n, d, h, w, cout, nullptr, c.tilesH, \
-                                                                         c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on(), slope, nmod0); \
-    } else {                                                                                                        \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march64_lw<G_, true, NQ_>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-    conv_fwd_march64_lw<G_, true, NQ_><<<grid, 512, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, \
-                                                                         (bf16_t*)y, ldy, n, d, h, w, cout, stats, c.tilesH, \
-                                                                         c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on()); \
-    }                                                                                                               \
+    if (lw64) launch(M64_KERNEL(conv_fwd_march64_lw, G_, true), 512, G_::LDS);                                       \
+    else if (twod) launch(M64_KERNEL(conv_fwd_march64, G_, true), G_::THREADS, G_::LDS);                             \
+    else launch(M64_KERNEL(conv_fwd_march64, G_, false), G_::THREADS, G_::LDS);                                      \
   } while (0)
-#define LAUNCH_M64(G_, TWOD_)                                                                                       \
-  do { if (cin == 128) LAUNCH_M64Q(G_, TWOD_, 4); else LAUNCH_M64Q(G_, TWOD_, 2); } while (0)
-#define LAUNCH_M64_2D(G_)                                                                                           \
-  do {                                                                                                              \
-    if (lw64) { if (cin == 128) LAUNCH_M64LW(G_, 4); else LAUNCH_M64LW(G_, 2); }                                    \
-    else LAUNCH_M64(G_, true);                                                                                      \
-  } while (0)
-    using G16 = MG64T<16>;
-    if (c.fw == 16) { if (twod) LAUNCH_M64_2D(G16); else LAUNCH_M64(G16, false); }
-    else { if (twod) LAUNCH_M64_2D(MG64); else LAUNCH_M64(MG64, false); }
-#undef LAUNCH_M64_2D
-#undef LAUNCH_M64
-#undef LAUNCH_M64LW
-#undef LAUNCH_M64Q
+    if (c.fw == 16) M64_FOOTPRINT(MG64T<16>); else M64_FOOTPRINT(MG64);
+#undef M64_FOOTPRINT
+#undef M64_KERNEL
     const int rc64 = fplx_check_launch("march64_conv3d_fwd");
     return rc64 < 0 ? rc64 : 1;
   }
@@ -1732,55 +1707,24 @@ extern "C" int fplx_march_conv3d_fwd_act(const void* x, int64_t ldx, const void*
   {
     const int kv2 = (int)fplx_knob(FPLX_K_MARCH32_V2);       // A/B knob
     if (kv2 && !twod && h % MG2::FH == 0 && w % MG2::FW == 0 && (int64_t)d * h * w * ldx * 2 <= ((int64_t)1 << 30)) {
-#define LAUNCH_M32V2(STATS_)                                                                                        \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march32v2<STATS_>, hipFuncAttributeMaxDynamicSharedMemorySize, MG2::LDS); \
-    conv_fwd_march32v2<STATS_><<<grid, MG2::THREADS, MG2::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, \
-                                                                ldy, n, d, h, w, cout, stats, c.tilesH, c.tilesW, c.dsegs, \
-                                                                c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on()); \
-  } while (0)
-#define LAUNCH_M32V3X(STATS_, ASWZ_)                                                                                      \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march32v3<STATS_, ASWZ_>, hipFuncAttributeMaxDynamicSharedMemorySize, MG2::LDS); \
-    conv_fwd_march32v3<STATS_, ASWZ_><<<grid, MG2::THREADS, MG2::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, \
-                                                                ldy, n, d, h, w, cout, stats, c.tilesH, c.tilesW, c.dsegs, \
-                                                                c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on()); \
-  } while (0)
-#define LAUNCH_M32V3(STATS_) LAUNCH_M32V3X(STATS_, 1)      /* ASWZ = 0: the 32 x 32 x 16 kernels' swizzle (A/B builds) */
+      auto launch = [&](auto kernel, auto... slope_arg) {       // (conv_fwd_march32v2 has no activation form: no slope parameter)
+        fplx_launch(kernel, grid, MG2::THREADS, MG2::LDS, st, (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h,
+                    w, cout, slope ? nullptr : stats, c.tilesH, c.tilesW, c.dsegs, c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32,
+                    fplx_xcd_on(), slope_arg...);
+      };
       // 1: v2 everywhere; 3: v3 everywhere; 4: v3 where no statistics are wanted (its STATS form spills), v2 otherwise
-      if (slope) {
-        (void)hipFuncSetAttribute((const void*)conv_fwd_march32v3<false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MG2::LDS);
-        conv_fwd_march32v3<false, 1, true><<<grid, MG2::THREADS, MG2::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y,
-                                                                ldy, n, d, h, w, cout, nullptr, c.tilesH, c.tilesW, c.dsegs,
-                                                                c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on(), slope);
-      }
-      else if (stats) { if (kv2 == 3) LAUNCH_M32V3(true); else LAUNCH_M32V2(true); }
-      else { if (kv2 >= 3) LAUNCH_M32V3(false); else LAUNCH_M32V2(false); }
-#undef LAUNCH_M32V3
-#undef LAUNCH_M32V3X
-#undef LAUNCH_M32V2
+      // (conv_fwd_march32v3<STATS, ASWZ, ACT>: ASWZ = 0 is the 32 x 32 x 16 kernels' swizzle, A/B builds)
+      if (slope) launch(conv_fwd_march32v3<false, 1, true>, slope);
+      else if (stats) { if (kv2 == 3) launch(conv_fwd_march32v3<true, 1>, nullptr); else launch(conv_fwd_march32v2<true>); }
+      else { if (kv2 >= 3) launch(conv_fwd_march32v3<false, 1>, nullptr); else launch(conv_fwd_march32v2<false>); }
       const int rc2 = fplx_check_launch("march32v2_conv3d_fwd");
       return rc2 < 0 ? rc2 : 1;
     }
   }
-#define LAUNCH_M32(TWOD_)                                                                                           \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march32<TWOD_>, hipFuncAttributeMaxDynamicSharedMemorySize, MG::LDS); \
-    conv_fwd_march32<TWOD_><<<grid, MG::THREADS, MG::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, \
-                                                                ldy, n, d, h, w, cout, stats, c.tilesH, c.tilesW, c.dsegs, \
-                                                                c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on()); \
-  } while (0)
-#define LAUNCH_M32A(TWOD_)                                                                                          \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_march32<TWOD_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MG::LDS); \
-    conv_fwd_march32<TWOD_, true><<<grid, MG::THREADS, MG::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, \
-                                                                ldy, n, d, h, w, cout, nullptr, c.tilesH, c.tilesW, c.dsegs, \
-                                                                c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on(), slope); \
-  } while (0)
-  if (slope) { if (twod) LAUNCH_M32A(true); else LAUNCH_M32A(false); }
-  else if (twod) LAUNCH_M32(true); else LAUNCH_M32(false);
-#undef LAUNCH_M32A
-#undef LAUNCH_M32
+  const auto k = slope ? (twod ? conv_fwd_march32<true, true> : conv_fwd_march32<false, true>)       // <TWOD, ACT>
+                       : (twod ? conv_fwd_march32<true> : conv_fwd_march32<false>);
+  fplx_launch(k, grid, MG::THREADS, MG::LDS, st, (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cout,
+              slope ? nullptr : stats, c.tilesH, c.tilesW, c.dsegs, c.dlen, (bf16_t*)y1, y1 ? cout / 64 : cout / 32, fplx_xcd_on(), slope);
   const int rc = fplx_check_launch("march_conv3d_fwd");
   return rc < 0 ? rc : 1;
 }

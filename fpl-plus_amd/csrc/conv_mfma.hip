@@ -8,7 +8,7 @@
 //                   Operand fragments are loaded straight from global/L2 (16 B per lane), no LDS:
 //                   the universal path (any spatial size, Cin % 16 == 0, Cout % 32 == 0).  With the
 //                   mirrored pack it is also the data-gradient kernel.
-#include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 
 namespace {
@@ -2215,200 +2215,156 @@ inline bool mfma_applicable(int64_t ldx, int64_t ldy, int cin, int cout, const v
 
 }  // namespace
 
-// conv_march.hip
-extern "C" int fplx_march_ok(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_march_rows(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_march_variant(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_march_conv3d_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                     int n, int d, int h, int w, int cin, int cout, float* stats, hipStream_t st,
-                                     const void* x1, void* y1, int twod);
-extern "C" int fplx_march_conv3d_fwd_act(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                         int n, int d, int h, int w, int cin, int cout, float* stats, hipStream_t st,
-                                         const void* x1, void* y1, int twod, const float* slope, int nmod0);
-extern "C" int fplx_brick_conv3d_fwd_act(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                         int n, int d, int h, int w, int cin, int cout, float* stats, float* partial, int geo,
-                                         int ksplit, hipStream_t st, const float* slope, const void* x1, int nmod0);
-// conv_brick.hip
-extern "C" int fplx_brick_ok(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_brick_first(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_brick_plan(int n, int d, int h, int w, int cin, int cout, int* geo, int* ksplit, int* bricks);
-extern "C" int fplx_brick_conv3d_fwd_ex(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
-                                        int n, int d, int h, int w, int cin, int cout, float* stats, float* partial, int geo,
-                                        int ksplit, hipStream_t st);
 static inline int splitk_fin_blocks(int64_t V) {
   const int64_t fb = (V + 7) / 8;
   return (int)(fb > 512 ? 512 : (fb < 1 ? 1 : fb));
 }
-static inline int brick_stats_rows(int n, int d, int h, int w, int cin, int cout) {
-  int geo, ks, bricks;
-  fplx_brick_plan(n, d, h, w, cin, cout, &geo, &ks, &bricks);
-  return ks > 1 ? splitk_fin_blocks((int64_t)n * d * h * w) : bricks;
-}
-static inline size_t brick_ws_bytes(int n, int d, int h, int w, int cin, int cout) {
-  int geo, ks, bricks;
-  fplx_brick_plan(n, d, h, w, cin, cout, &geo, &ks, &bricks);
-  return ks > 1 ? (size_t)ks * n * d * h * w * cout * sizeof(float) : 0;
-}
 
-// mid != 0: the 27-tap pack is zero outside the middle depth plane (a Conv2d per depth slice, 2.5D levels).  Layers that
-// would go to the tile kernel run taps 9..17 only (measured 348 -> 155 us on the 128 -> 64 level-1 layer of the shipped
-// config); where a march kernel applies it keeps all 27 taps - its 1.0 PFLOP/s on three times the work still beats the
-// tile kernel's short-K form (111 vs 117 us at 64 -> 64, 52 vs 70 us at 32 -> 64).  Same result either way.
-static inline bool mid_tile(int mid, int n, int d, int h, int w, int cin, int cout) {
-  const bool on = fplx_knob(FPLX_K_MID_TILE) != 0;          // A/B knob
-  return mid && on && cin % 32 == 0 && cout % 64 == 0 && !fplx_march_ok(n, d, h, w, cin, cout) &&
-         !stream_ok(d, h, w, cin, cout);
-}
+// ---- the plan of the 3x3x3 bf16 forward: which kernel family runs a layer and everything that follows from it, a pure
+// function of the shape and the tuning table.  The size queries (statistics rows, workspace), the plan query, the
+// activation-form queries and the launcher all read THIS plan: the dispatch order is written once, in fwd_plan.
+// mid != 0: the 27-tap pack is zero outside the middle depth plane (a Conv2d per depth slice, 2.5D levels).
+struct FwdPlan {
+  int kernel;                 // FPLX_KERNEL_*; GENERIC: not an MFMA layer (channel counts)
+  int geo;                    // brick: geometry; march: fplx_march_variant; else -1
+  int ksplit;                 // reduction split (brick: over Cin, tile / direct: over the taps); > 1: splitk_finish_k finishes
+  int stats_rows;             // rows of the BatchNorm partial statistics the launch writes
+  size_t ws_bytes;            // split-K partials fp32 [ksplit][V][cout]; 0 without a split
+  int tap_lo, tap_cnt;        // taps the tile kernel runs: 0 / 27, or 9 / 9 (mid)
+  bool fits;                  // voxel indices fit 31 bits: the launchers and the plan query decline the layer otherwise
+  StreamCfg stream;           // STREAM
+  DirectCfg direct;           // TILE, DIRECT
+};
 
-static int stats_rows_impl(int n, int d, int h, int w, int cin, int cout, int mid) {
-  if (cin % 16 != 0 || cout % 32 != 0) return 0;
+static FwdPlan fwd_plan(int n, int d, int h, int w, int cin, int cout, int mid) {
+  FwdPlan p = {};
+  p.kernel = FPLX_KERNEL_GENERIC; p.geo = -1; p.ksplit = 1; p.tap_cnt = 27;
+  if (cin % 16 != 0 || cout % 32 != 0) return p;
   const int64_t V = (int64_t)n * d * h * w;
-  if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) return brick_stats_rows(n, d, h, w, cin, cout);
-  if (fplx_march_ok(n, d, h, w, cin, cout)) return fplx_march_rows(n, d, h, w, cin, cout);
-  if (stream_ok(d, h, w, cin, cout)) return stream_cfg(n, d, h, w, cout).nblk;
-  if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) return brick_stats_rows(n, d, h, w, cin, cout);
-  const DirectCfg c = direct_cfg(V, cin, cout, mid_tile(mid, n, d, h, w, cin, cout) ? 9 : 27);
-  if (c.ksplit > 1) return c.fin_blocks;
-  return (int)c.mblocks;
+  p.fits = V < ((int64_t)1 << 31);
+  auto split = [&](int rows) {                                // a split launch: the finish kernel writes the statistics rows
+    p.stats_rows = p.ksplit > 1 ? splitk_fin_blocks(V) : rows;
+    p.ws_bytes = p.ksplit > 1 ? (size_t)p.ksplit * V * cout * sizeof(float) : 0;
+  };
+  auto brick = [&]() {
+    int bricks;
+    fplx_brick_plan(n, d, h, w, cin, cout, &p.geo, &p.ksplit, &bricks);
+    p.kernel = FPLX_KERNEL_BRICK;
+    split(bricks);
+  };
+  // the order: brick ahead of the march kernels where it is the faster one (fplx_brick_first), the depth marches, their
+  // predecessor (knob march = 0 | 2), brick on the layers no march kernel takes, the tile / direct implicit GEMM
+  if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) { brick(); return p; }
+  if (fplx_march_ok(n, d, h, w, cin, cout)) {
+    // (mid: the march keeps all 27 taps - its 1.0 PFLOP/s on three times the work still beats the tile kernel's short-K
+    // form: 111 vs 117 us at 64 -> 64, 52 vs 70 us at 32 -> 64)
+    p.kernel = FPLX_KERNEL_MARCH;
+    p.geo = fplx_march_variant(n, d, h, w, cin, cout);
+    p.stats_rows = fplx_march_rows(n, d, h, w, cin, cout);
+    return p;
+  }
+  if (stream_ok(d, h, w, cin, cout)) {
+    p.kernel = FPLX_KERNEL_STREAM;
+    p.stream = stream_cfg(n, d, h, w, cout);
+    p.stats_rows = p.stream.nblk;
+    return p;
+  }
+  if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) { brick(); return p; }
+  // mid: layers of the tile kernel run taps 9..17 only (measured 348 -> 155 us on the 128 -> 64 level-1 layer of the shipped
+  // config; A/B knob mid_tile).  Same result either way.
+  if (mid && fplx_knob(FPLX_K_MID_TILE) != 0 && cin % 32 == 0 && cout % 64 == 0) { p.tap_lo = 9; p.tap_cnt = 9; }
+  p.direct = direct_cfg(V, cin, cout, p.tap_cnt);
+  p.kernel = p.direct.tile_nt ? FPLX_KERNEL_TILE : FPLX_KERNEL_DIRECT;
+  p.ksplit = p.direct.ksplit;
+  split((int)p.direct.mblocks);
+  return p;
 }
 
-static size_t fwd_ws_impl(int n, int d, int h, int w, int cin, int cout, int mid) {
-  if (cin % 16 != 0 || cout % 32 != 0) return 0;
-  if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) return brick_ws_bytes(n, d, h, w, cin, cout);
-  if (fplx_march_ok(n, d, h, w, cin, cout) || stream_ok(d, h, w, cin, cout)) return 0;
-  if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) return brick_ws_bytes(n, d, h, w, cin, cout);
-  const int64_t V = (int64_t)n * d * h * w;
-  const DirectCfg c = direct_cfg(V, cin, cout, mid_tile(mid, n, d, h, w, cin, cout) ? 9 : 27);
-  return c.ksplit > 1 ? (size_t)c.ksplit * V * cout * sizeof(float) : 0;
-}
-
-// the dispatch order of mfma_fwd_impl as data (fplx_conv3d_plan_query): kernel family, brick geometry, reduction split
+// the plan as data (fplx_conv3d_plan_query): kernel family, brick geometry / march variant, reduction split; returns 0 where
+// the generic kernel runs
 extern "C" int fplx_mfma_conv3d_plan(int n, int d, int h, int w, int cin, int cout, int mid, int* kernel, int* geo, int* ksplit) {
-  *kernel = FPLX_KERNEL_GENERIC; *geo = -1; *ksplit = 1;
-  if (cin % 16 != 0 || cout % 32 != 0 || (int64_t)n * d * h * w >= ((int64_t)1 << 31)) return 0;
-  auto brick = [&]() { int b; fplx_brick_plan(n, d, h, w, cin, cout, geo, ksplit, &b); *kernel = FPLX_KERNEL_BRICK; return 1; };
-  if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) return brick();
-  if (fplx_march_ok(n, d, h, w, cin, cout)) { *kernel = FPLX_KERNEL_MARCH; *geo = fplx_march_variant(n, d, h, w, cin, cout); return 1; }
-  if (stream_ok(d, h, w, cin, cout)) { *kernel = FPLX_KERNEL_STREAM; return 1; }
-  if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) return brick();
-  const DirectCfg c = direct_cfg((int64_t)n * d * h * w, cin, cout, mid_tile(mid, n, d, h, w, cin, cout) ? 9 : 27);
-  *kernel = c.tile_nt ? FPLX_KERNEL_TILE : FPLX_KERNEL_DIRECT;
-  *ksplit = c.ksplit;
-  return 1;
+  const FwdPlan p = fwd_plan(n, d, h, w, cin, cout, mid);
+  const bool ok = p.kernel != FPLX_KERNEL_GENERIC && p.fits;
+  *kernel = ok ? p.kernel : FPLX_KERNEL_GENERIC; *geo = ok ? p.geo : -1; *ksplit = ok ? p.ksplit : 1;
+  return ok;
+}
+extern "C" int fplx_mfma_conv3d_stats_rows(int n, int d, int h, int w, int cin, int cout, int mid) {
+  return fwd_plan(n, d, h, w, cin, cout, mid).stats_rows;
+}
+extern "C" size_t fplx_mfma_conv3d_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout, int mid) {
+  return fwd_plan(n, d, h, w, cin, cout, mid).ws_bytes;
 }
 
-extern "C" int fplx_mfma_conv3d_stats_rows(int n, int d, int h, int w, int cin, int cout) {
-  return stats_rows_impl(n, d, h, w, cin, cout, 0);
-}
-extern "C" int fplx_mfma_conv3d_mid_stats_rows(int n, int d, int h, int w, int cin, int cout) {
-  return stats_rows_impl(n, d, h, w, cin, cout, 1);
-}
-extern "C" size_t fplx_mfma_conv3d_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout) {
-  return fwd_ws_impl(n, d, h, w, cin, cout, 0);
-}
-extern "C" size_t fplx_mfma_conv3d_mid_fwd_ws_bytes(int n, int d, int h, int w, int cin, int cout) {
-  return fwd_ws_impl(n, d, h, w, cin, cout, 1);
-}
-
+// launches fwd_plan's kernel; 0 where the operands (alignment, leading dimensions) or the form asked for are not its own.
 // slope != NULL (inference: eval-mode BatchNorm folded into the pack): PReLU in the kernel's write-out or in the split-K
 // finish; the caller has checked fplx_mfma_conv3d_act_ok (the stream / unsplit tile / direct kernels have no such form)
 static int mfma_fwd_impl(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy, int n, int d,
                          int h, int w, int cin, int cout, float* stats, void* ws, size_t ws_bytes, int mid,
                          hipStream_t st, const float* slope = nullptr) {
-  if (!mfma_applicable(ldx, ldy, cin, cout, x, y, wp) || (int64_t)n * d * h * w >= ((int64_t)1 << 31)) return 0;
-  const bool midt = mid_tile(mid, n, d, h, w, cin, cout);
-  const int tap_lo = midt ? 9 : 0, tap_cnt = midt ? 9 : 27;
-  auto brick_launch = [&]() -> int {
-    int geo, ks, bricks;
-    fplx_brick_plan(n, d, h, w, cin, cout, &geo, &ks, &bricks);
-    const int64_t Vb = (int64_t)n * d * h * w;
-    if (ks > 1 && (!ws || ws_bytes < (size_t)ks * Vb * cout * sizeof(float)))
-      return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_fwd: split-K needs %zu workspace bytes (fplx_conv3d_fwd_ws_bytes)",
-                       (size_t)ks * Vb * cout * sizeof(float));
-    const int rb = fplx_brick_conv3d_fwd_act(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats,
-                                             (float*)ws, geo, ks, st, slope, nullptr, 0);
-    if (rb == 1 && ks > 1) {
-      splitk_finish_k<<<splitk_fin_blocks(Vb), 256, 0, st>>>((const float*)ws, ks, Vb, cout, bias, (bf16_t*)y, ldy, stats, slope);
-      const int rf = fplx_check_launch("brick_splitk_finish");
-      if (rf < 0) return rf;
-    }
-    return rb;
-  };
-  if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) return brick_launch();
-  if (fplx_march_ok(n, d, h, w, cin, cout))
-    return fplx_march_conv3d_fwd_act(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, st, nullptr, nullptr, mid, slope, 0);
-  if (stream_ok(d, h, w, cin, cout)) {
-    if (slope) return 0;
-    const StreamCfg sc = stream_cfg(n, d, h, w, cout);
-    dim3 grid(sc.nblk, cout / 32);
-    if (cin == 32) {
-      (void)hipFuncSetAttribute((const void*)conv_fwd_stream<32>, hipFuncAttributeMaxDynamicSharedMemorySize, StreamGeo<32>::LDS);
-      conv_fwd_stream<32><<<grid, 256, StreamGeo<32>::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y,
-                                                                ldy, n, d, h, w, cout, stats, sc.tilesH, sc.tilesW,
-                                                                sc.dsegs, sc.dlen);
-    } else {
-      (void)hipFuncSetAttribute((const void*)conv_fwd_stream<64>, hipFuncAttributeMaxDynamicSharedMemorySize, StreamGeo<64>::LDS);
-      conv_fwd_stream<64><<<grid, 256, StreamGeo<64>::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y,
-                                                                ldy, n, d, h, w, cout, stats, sc.tilesH, sc.tilesW,
-                                                                sc.dsegs, sc.dlen);
-    }
-    int rc0 = fplx_check_launch("mfma_conv3d_fwd_stream");
-    return rc0 < 0 ? rc0 : 1;
-  }
-  if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) return brick_launch();
+  if (!mfma_applicable(ldx, ldy, cin, cout, x, y, wp)) return 0;
+  const FwdPlan p = fwd_plan(n, d, h, w, cin, cout, mid);
+  if (!p.fits) return 0;
   const int64_t V = (int64_t)n * d * h * w;
-  const DirectCfg c = direct_cfg(V, cin, cout, tap_cnt);
-  const int ks = c.ksplit;
-  float* partial = nullptr;
-  if (slope && ks <= 1) return 0;                          // no activation form of the unsplit tile / direct kernels
-  if (ks > 1) {
-    // the statistics row count was promised for the split-K path: the workspace is mandatory here
-    if (!ws || ws_bytes < (size_t)ks * V * cout * sizeof(float))
-      return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_fwd: split-K needs %zu workspace bytes (fplx_conv3d_fwd_ws_bytes)",
-                       (size_t)ks * V * cout * sizeof(float));
-    partial = (float*)ws;
+  const int ks = p.ksplit;
+  // the statistics row count was promised for the split-K path: the workspace is mandatory there
+  if (ks > 1 && (!ws || ws_bytes < p.ws_bytes))
+    return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_fwd: split-K needs %zu workspace bytes (fplx_conv3d_fwd_ws_bytes)", p.ws_bytes);
+  float* partial = ks > 1 ? (float*)ws : nullptr;
+  switch (p.kernel) {
+    case FPLX_KERNEL_BRICK: {
+      const int rb = fplx_brick_conv3d_fwd_act(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, (float*)ws, p.geo, ks,
+                                               st, slope, nullptr, 0);
+      if (rb == 1 && ks > 1) {
+        splitk_finish_k<<<splitk_fin_blocks(V), 256, 0, st>>>((const float*)ws, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);
+        const int rf = fplx_check_launch("brick_splitk_finish");
+        if (rf < 0) return rf;
+      }
+      return rb;
+    }
+    case FPLX_KERNEL_MARCH:
+      return fplx_march_conv3d_fwd_act(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, st, nullptr, nullptr, mid, slope, 0);
+    case FPLX_KERNEL_STREAM: {
+      if (slope) return 0;
+      const StreamCfg& sc = p.stream;
+      const auto k = cin == 32 ? conv_fwd_stream<32> : conv_fwd_stream<64>;
+      fplx_launch(k, dim3(sc.nblk, cout / 32), 256, cin == 32 ? StreamGeo<32>::LDS : StreamGeo<64>::LDS, st, (const bf16_t*)x, ldx,
+                  (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cout, stats, sc.tilesH, sc.tilesW, sc.dsegs, sc.dlen);
+      int rc0 = fplx_check_launch("mfma_conv3d_fwd_stream");
+      return rc0 < 0 ? rc0 : 1;
+    }
+    case FPLX_KERNEL_TILE: {
+      if (slope && ks <= 1) return 0;                          // no activation form of the unsplit tile kernel
+      const DirectCfg& c = p.direct;
+      const bool k64 = cin % 64 == 0;
+      const int kc = (c.tile_mt == 256 || k64) ? 64 : 32;
+      const auto k = c.tile_mt == 256 ? (c.tile_nt == 128 ? conv_fwd_tile<128, 64, 256> : conv_fwd_tile<64, 64, 256>)
+                     : c.tile_nt == 128 ? (k64 ? conv_fwd_tile<128, 64, 128> : conv_fwd_tile<128, 32, 128>)
+                                        : (k64 ? conv_fwd_tile<64, 64, 128> : conv_fwd_tile<64, 32, 128>);
+      fplx_launch(k, dim3((unsigned)c.mblocks, cout / c.tile_nt, ks), c.tile_mt * 2, (size_t)2 * (c.tile_mt + c.tile_nt) * kc * 2, st,
+                  (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, stats, partial, p.tap_lo,
+                  p.tap_cnt, fplx_xcd_on());
+      if (ks > 1) splitk_finish_k<<<c.fin_blocks, 256, 0, st>>>(partial, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);
+      int rct = fplx_check_launch("mfma_conv3d_fwd_tile");
+      return rct < 0 ? rct : 1;
+    }
+    case FPLX_KERNEL_DIRECT: {
+      if (slope && ks <= 1) return 0;                          // no activation form of the unsplit direct kernel
+      const DirectCfg& c = p.direct;
+      const auto k = c.ntl == 2 ? conv_fwd_direct<2, 2, 0> : conv_fwd_direct<4, 1, 0>;
+      fplx_launch(k, dim3((unsigned)c.mblocks, cout / (c.ntl * 32), ks), DIRECT_THREADS, 0, st, (const bf16_t*)x, ldx,
+                  (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, stats, partial);
+      if (ks > 1) splitk_finish_k<<<c.fin_blocks, 256, 0, st>>>(partial, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);
+      int rc = fplx_check_launch("mfma_conv3d_fwd");
+      return rc < 0 ? rc : 1;
+    }
+    default: return 0;
   }
-  if (c.tile_nt) {
-    dim3 tg((unsigned)c.mblocks, cout / c.tile_nt, ks);
-#define LAUNCH_TILE(NT_, KC_, MT_)                                                                                \
-  do {                                                                                                              \
-    constexpr int LDS = 2 * (MT_ + NT_) * KC_ * 2;                                                                  \
-    (void)hipFuncSetAttribute((const void*)conv_fwd_tile<NT_, KC_, MT_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); \
-    conv_fwd_tile<NT_, KC_, MT_><<<tg, MT_ * 2, LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, \
-                                                           n, d, h, w, cin, cout, stats, partial, tap_lo, tap_cnt, fplx_xcd_on()); \
-  } while (0)
-    const bool k64 = cin % 64 == 0;
-    if (c.tile_mt == 256) { if (c.tile_nt == 128) LAUNCH_TILE(128, 64, 256); else LAUNCH_TILE(64, 64, 256); }
-    else if (c.tile_nt == 128) { if (k64) LAUNCH_TILE(128, 64, 128); else LAUNCH_TILE(128, 32, 128); }
-    else { if (k64) LAUNCH_TILE(64, 64, 128); else LAUNCH_TILE(64, 32, 128); }
-#undef LAUNCH_TILE
-    if (ks > 1) splitk_finish_k<<<c.fin_blocks, 256, 0, st>>>(partial, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);
-    int rct = fplx_check_launch("mfma_conv3d_fwd_tile");
-    return rct < 0 ? rct : 1;
-  }
-  dim3 grid((unsigned)((V + 4 * c.mt * 32 - 1) / (4 * c.mt * 32)), cout / (c.ntl * 32), ks);
-  if (c.ntl == 2)
-    conv_fwd_direct<2, 2, 0><<<grid, DIRECT_THREADS, 0, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y,
-                                                           ldy, n, d, h, w, cin, cout, stats, partial);
-  else
-    conv_fwd_direct<4, 1, 0><<<grid, DIRECT_THREADS, 0, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y,
-                                                           ldy, n, d, h, w, cin, cout, stats, partial);
-  if (ks > 1)
-    splitk_finish_k<<<c.fin_blocks, 256, 0, st>>>(partial, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);
-  int rc = fplx_check_launch("mfma_conv3d_fwd");
-  return rc < 0 ? rc : 1;
 }
 
-// returns 1 if handled, 0 if not applicable (caller falls back to the generic kernel), <0 on error
 extern "C" int fplx_mfma_conv3d_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy,
                                     int n, int d, int h, int w, int cin, int cout, float* stats, void* ws,
-                                    size_t ws_bytes, hipStream_t st) {
-  return mfma_fwd_impl(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, ws, ws_bytes, 0, st);
-}
-extern "C" int fplx_mfma_conv3d_mid_fwd(const void* x, int64_t ldx, const void* wp, const float* bias, void* y,
-                                        int64_t ldy, int n, int d, int h, int w, int cin, int cout, float* stats, void* ws,
-                                        size_t ws_bytes, hipStream_t st) {
-  return mfma_fwd_impl(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, ws, ws_bytes, 1, st);
+                                    size_t ws_bytes, int mid, hipStream_t st) {
+  return mfma_fwd_impl(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, ws, ws_bytes, mid, st);
 }
 
 // 1 if the layer's forward kernel has the PReLU write-out (or finishes through splitk_finish_k)
@@ -2419,25 +2375,26 @@ static inline bool act_sample_fits(int d, int h, int w, int cin) {
   return (int64_t)d * h * w * (2 * cin) * 2 < ((int64_t)1 << 30);
 }
 extern "C" int fplx_mfma_conv3d_act_ok(int n, int d, int h, int w, int cin, int cout, int mid) {
-  int kernel, geo, ks;
   if (!act_sample_fits(d, h, w, cin)) return 0;
-  if (!fplx_mfma_conv3d_plan(n, d, h, w, cin, cout, mid, &kernel, &geo, &ks)) return 0;
-  return kernel == FPLX_KERNEL_BRICK || kernel == FPLX_KERNEL_MARCH || ((kernel == FPLX_KERNEL_TILE || kernel == FPLX_KERNEL_DIRECT) && ks > 1);
+  const FwdPlan p = fwd_plan(n, d, h, w, cin, cout, mid);
+  if (!p.fits) return 0;
+  return p.kernel == FPLX_KERNEL_BRICK || p.kernel == FPLX_KERNEL_MARCH ||
+         ((p.kernel == FPLX_KERNEL_TILE || p.kernel == FPLX_KERNEL_DIRECT) && p.ksplit > 1);
 }
 // the two-tensor input (x0 || x1, Cin / 2 channels each, one leading dimension; x0 read modulo nmod0 samples) of the brick
-// kernel's activation form: the 3D layers it takes first, unsplit in Cin
+// kernel's activation form: the 3D layers it takes, unsplit in Cin
+static inline bool act_cat2_plan(const FwdPlan& p, int d, int h, int w, int cin, int mid) {
+  return !mid && cin % 64 == 0 && act_sample_fits(d, h, w, cin) && p.fits && p.kernel == FPLX_KERNEL_BRICK && p.ksplit == 1;
+}
 extern "C" int fplx_mfma_conv3d_act_cat2_ok(int n, int d, int h, int w, int cin, int cout, int mid) {
-  int kernel, geo, ks;
-  if (mid || cin % 64 != 0 || !act_sample_fits(d, h, w, cin) || !fplx_mfma_conv3d_plan(n, d, h, w, cin, cout, mid, &kernel, &geo, &ks)) return 0;
-  return kernel == FPLX_KERNEL_BRICK && ks == 1;
+  return act_cat2_plan(fwd_plan(n, d, h, w, cin, cout, mid), d, h, w, cin, mid);
 }
 extern "C" int fplx_mfma_conv3d_fwd_act_cat2(const void* x0, const void* x1, int64_t ldx, const void* wp, const float* bias,
                                              const float* slope, void* y, int64_t ldy, int n, int d, int h, int w, int cin,
                                              int cout, int nmod0, hipStream_t st) {
-  if (!fplx_mfma_conv3d_act_cat2_ok(n, d, h, w, cin, cout, 0) || !mfma_applicable(ldx, ldy, cin, cout, x0, y, wp)) return 0;
-  int geo, ks, bricks;
-  fplx_brick_plan(n, d, h, w, cin, cout, &geo, &ks, &bricks);
-  return fplx_brick_conv3d_fwd_act(x0, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, nullptr, nullptr, geo, ks, st, slope, x1, nmod0);
+  const FwdPlan p = fwd_plan(n, d, h, w, cin, cout, 0);
+  if (!act_cat2_plan(p, d, h, w, cin, 0) || !mfma_applicable(ldx, ldy, cin, cout, x0, y, wp)) return 0;
+  return fplx_brick_conv3d_fwd_act(x0, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, nullptr, nullptr, p.geo, p.ksplit, st, slope, x1, nmod0);
 }
 extern "C" int fplx_mfma_conv3d_fwd_act(const void* x, int64_t ldx, const void* wp, const float* bias, const float* slope, void* y,
                                         int64_t ldy, int n, int d, int h, int w, int cin, int cout, void* ws, size_t ws_bytes,
@@ -2445,14 +2402,32 @@ extern "C" int fplx_mfma_conv3d_fwd_act(const void* x, int64_t ldx, const void* 
   return mfma_fwd_impl(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, nullptr, ws, ws_bytes, mid, st, slope);
 }
 
-// conv_wgrad.hip (rolling-window weight gradient): same partial-tile format, reduced by wgrad_stream_reduce
-extern "C" int fplx_wgroll_ok(int n, int d, int h, int w, int cin, int cout, int64_t ldx, int64_t ldy);
-extern "C" size_t fplx_wgroll_ws_bytes(int n, int d, int h, int w, int cin, int cout);
-extern "C" int fplx_wgroll_conv3d_wgrad(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, int n, int d, int h,
-                                        int w, int cin, int cout, void* ws, size_t ws_bytes, hipStream_t st, const void* x1, int mid);
+// ---- the plan of the 3x3x3 bf16 weight gradient: which of the three kernels runs a layer, and its workspace.  All three
+// write per-block partial tiles in one format, summed in a fixed order by wgrad_finish.
+//   mid: a Conv2d per depth slice (middle-plane taps only); splitx: x given as two tensors of Cin / 2 channels
+enum { WG_VOX, WG_ROLL, WG_STREAM };
+struct WgradPlan { int kernel; size_t ws_bytes; VoxCfg vox; WgCfg stream; };      // vox / stream: the chosen kernel's only
+
+static WgradPlan wgrad_plan(int n, int d, int h, int w, int cin, int cout, int mid, int splitx) {
+  WgradPlan p = {};
+  // the order: voxel GEMM (small deep volumes, 3D one-tensor form only), the rolling window (conv_wgrad.hip), the footprint march
+  if (!splitx && !mid) {
+    p.vox = vox_cfg(n, d, h, w, cin, cout);
+    if (p.vox.ok) { p.kernel = WG_VOX; p.ws_bytes = p.vox.ws; return p; }
+  }
+  if (fplx_wgroll_ok(n, d, h, w, cin, cout, mid, splitx)) {
+    p.kernel = WG_ROLL;
+    p.ws_bytes = fplx_wgroll_ws_bytes(n, d, h, w, cin, cout);
+    return p;
+  }
+  p.kernel = WG_STREAM;
+  p.stream = wg_cfg(n, d, h, w, cin, cout);
+  p.ws_bytes = p.stream.ws;
+  return p;
+}
+
 extern "C" int fplx_wgrad_reduce_launch(const float* part, int nblk, int npairs, int cin, int cout, float* dw, int mid,
                                         hipStream_t st) {
-  const int64_t total = (int64_t)npairs * 27 * 1024;
   wgrad_finish(part, nblk, npairs, cin, cout, dw, mid, st);
   return fplx_check_launch("wgrad_stream_reduce");
 }
@@ -2462,12 +2437,16 @@ extern "C" int fplx_mfma_conv3d_wgrad_cit(int n, int d, int h, int w, int cin, i
   return wg_cfg(n, d, h, w, cin, cout).cit;
 }
 
+// NOT the chosen kernel's workspace but the maximum over the kernels a knob could switch the layer to: callers allocate
+// once per step and size the buffer before they know the form (the 2.5D form of a layer never takes the voxel GEMM, a
+// split x never the 3D rolling window) or the knobs (wg_vox, wg_roll, wg_roll2d may be flipped between steps); the
+// footprint march is every layer's last resort.
 extern "C" size_t fplx_mfma_conv3d_wgrad_ws_bytes(int n, int d, int h, int w, int cin, int cout) {
   if (cin % 32 != 0 || cout % 32 != 0) return 0;
-  const size_t a = wg_cfg(n, d, h, w, cin, cout).ws;
-  const VoxCfg v = vox_cfg(n, d, h, w, cin, cout);          // the largest of the three: the 2.5D form of a layer never takes vox
-  size_t m = (v.ok && v.ws > a) ? v.ws : a;                 // or the rolling-window kernel, and a knob may switch kernels
-  if (fplx_wgroll_ok(n, d, h, w, cin, cout, cin, cout)) { const size_t r = fplx_wgroll_ws_bytes(n, d, h, w, cin, cout); if (r > m) m = r; }
+  size_t m = wg_cfg(n, d, h, w, cin, cout).ws;
+  const VoxCfg v = vox_cfg(n, d, h, w, cin, cout);
+  if (v.ok && v.ws > m) m = v.ws;
+  if (fplx_wgroll_ok(n, d, h, w, cin, cout, 0, 0)) { const size_t r = fplx_wgroll_ws_bytes(n, d, h, w, cin, cout); if (r > m) m = r; }
   return m;
 }
 
@@ -2478,49 +2457,36 @@ extern "C" int fplx_mfma_conv3d_wgrad(const void* x, int64_t ldx, const void* dy
                                       const void* x1, int mid) {
   if (cin % 32 != 0 || cout % 32 != 0 || ldx % 8 != 0 || ldy % 8 != 0 || ((uintptr_t)x % 16) || ((uintptr_t)dy % 16))
     return 0;
-  if (!x1 && !mid) {
-    const VoxCfg v = vox_cfg(n, d, h, w, cin, cout);
-    if (v.ok) {
-      if (ws_bytes < v.ws) return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_wgrad: workspace %zu < %zu", ws_bytes, v.ws);
-      dim3 grid(v.g.S, v.npairs / v.cot);
-      const int lwk = (int)fplx_knob(FPLX_K_WG_VOX_LW);
-      if ((lwk == 2 || (lwk == 1 && v.g.V <= 2048)) && v.cot == 1 && (int64_t)v.g.V * ldx * 2 < ((int64_t)1 << 31) &&
-          (int64_t)v.g.V * ldy * 2 < ((int64_t)1 << 31)) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_vox_lw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
-        conv_wgrad_vox_lw<<<grid, 512, v.lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, cin, cout, v.g, fplx_xcd_on());
-      } else if (v.cot == 2) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_vox<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
-        conv_wgrad_vox<2><<<grid, 256, v.lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, cin, cout, v.g, fplx_xcd_on());
-      } else {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_vox<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
-        conv_wgrad_vox<1><<<grid, 256, v.lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, cin, cout, v.g, fplx_xcd_on());
-      }
-      wgrad_finish((const float*)ws, v.g.S, v.npairs, cin, cout, dw, 0, st);
-      int rcv = fplx_check_launch("mfma_conv3d_wgrad_vox");
-      return rcv < 0 ? rcv : 1;
-    }
+  WgradPlan p = wgrad_plan(n, d, h, w, cin, cout, mid, x1 != nullptr);
+  if (p.kernel == WG_VOX) {
+    const VoxCfg& v = p.vox;
+    if (ws_bytes < v.ws) return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_wgrad: workspace %zu < %zu", ws_bytes, v.ws);
+    const int lwk = (int)fplx_knob(FPLX_K_WG_VOX_LW);
+    const bool lw = (lwk == 2 || (lwk == 1 && v.g.V <= 2048)) && v.cot == 1 && (int64_t)v.g.V * ldx * 2 < ((int64_t)1 << 31) &&
+                    (int64_t)v.g.V * ldy * 2 < ((int64_t)1 << 31);
+    const auto k = lw ? conv_wgrad_vox_lw : v.cot == 2 ? conv_wgrad_vox<2> : conv_wgrad_vox<1>;
+    fplx_launch(k, dim3(v.g.S, v.npairs / v.cot), lw ? 512 : 256, v.lds, st, (const bf16_t*)x, ldx, (const bf16_t*)dy, ldy,
+                (float*)ws, cin, cout, v.g, fplx_xcd_on());
+    wgrad_finish((const float*)ws, v.g.S, v.npairs, cin, cout, dw, 0, st);
+    int rcv = fplx_check_launch("mfma_conv3d_wgrad_vox");
+    return rcv < 0 ? rcv : 1;
   }
-  {                                                         // the rolling-window kernels (conv_wgrad.hip) where they apply
+  if (p.kernel == WG_ROLL) {
     const int rr = fplx_wgroll_conv3d_wgrad(x, ldx, dy, ldy, dw, n, d, h, w, cin, cout, ws, ws_bytes, st, x1, mid);
     if (rr != 0) return rr;
+    p.stream = wg_cfg(n, d, h, w, cin, cout);                 // operands it declines (a sample of 1 GiB in ldx, x1's alignment)
   }
-  const WgCfg c = wg_cfg(n, d, h, w, cin, cout);
+  const WgCfg& c = p.stream;
   if (x1 && (c.cit != 2 || cin != 64 || ((uintptr_t)x1 % 16))) return 0;   // split x: one group of two ci tiles
   if (ws_bytes < c.ws) return fplx_fail(FPLX_E_WORKSPACE, "mfma_conv3d_wgrad: workspace %zu < %zu", ws_bytes, c.ws);
-  dim3 grid(c.nblk, c.npairs / (c.cit * c.cot));
-#define LAUNCH_WG2(TW_, CIT_, COT_, TWOD_)                                                                          \
-  do {                                                                                                              \
-    const size_t lds = (size_t)(3 * CIT_ * (WG_TH + 2) * (TW_ + 2) + COT_ * WG_TH * TW_) * 64;                      \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_stream<TW_, CIT_, COT_, TWOD_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    conv_wgrad_stream<TW_, CIT_, COT_, TWOD_><<<grid, 256, lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, n, d, \
-                                                                h, w, cin, cout, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on()); \
-  } while (0)
-#define LAUNCH_WG(TW_, CIT_, COT_) do { if (mid) LAUNCH_WG2(TW_, CIT_, COT_, true); else LAUNCH_WG2(TW_, CIT_, COT_, false); } while (0)
-  if (c.tw == 32) { if (c.cot == 2) LAUNCH_WG(32, 1, 2); else if (c.cit == 2) LAUNCH_WG(32, 2, 1); else LAUNCH_WG(32, 1, 1); }
-  else { if (c.cot == 2) LAUNCH_WG(16, 1, 2); else if (c.cit == 2) LAUNCH_WG(16, 2, 1); else LAUNCH_WG(16, 1, 1); }
-#undef LAUNCH_WG
-#undef LAUNCH_WG2
-  const int64_t total = (int64_t)c.npairs * 27 * 1024;
+#define WG_KERNEL(TW_, CIT_, COT_) (mid ? conv_wgrad_stream<TW_, CIT_, COT_, true> : conv_wgrad_stream<TW_, CIT_, COT_, false>)
+  const int tw = c.tw == 32 ? 32 : 16, cot = c.cot == 2 ? 2 : 1, cit = (cot == 1 && c.cit == 2) ? 2 : 1;   // the instantiations
+  const auto k = tw == 32 ? (cot == 2 ? WG_KERNEL(32, 1, 2) : cit == 2 ? WG_KERNEL(32, 2, 1) : WG_KERNEL(32, 1, 1))
+                          : (cot == 2 ? WG_KERNEL(16, 1, 2) : cit == 2 ? WG_KERNEL(16, 2, 1) : WG_KERNEL(16, 1, 1));
+#undef WG_KERNEL
+  fplx_launch(k, dim3(c.nblk, c.npairs / (c.cit * c.cot)), 256, (size_t)(3 * cit * (WG_TH + 2) * (tw + 2) + cot * WG_TH * tw) * 64, st,
+              (const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, n, d, h, w, cin, cout, c.tilesH, c.tilesW, c.dsegs, c.dlen,
+              (const bf16_t*)x1, fplx_xcd_on());
   wgrad_finish((const float*)ws, c.nblk, c.npairs, cin, cout, dw, mid, st);
   int rc = fplx_check_launch("mfma_conv3d_wgrad");
   return rc < 0 ? rc : 1;
@@ -2541,13 +2507,13 @@ extern "C" int fplx_mfma_deconv2_fwd(const void* x, int64_t ldx, const void* wf,
                                                          (ks == 4 && ntc == 2))) {
       const int64_t nt = (V + 31) / 32;
       const unsigned nb = (unsigned)(nt < 1024 ? nt : 1024);
-#define LAUNCH_DR(KS_, NTC_) deconv_fwd_rows<KS_, NTC_><<<nb, 256, 0, st>>>((const bf16_t*)x, ldx, (const bf16_t*)wf, bias, \
-                                                                           (bf16_t*)y, ldy, n, d, h, w, fplx_xcd_on())
-      if (ks == 4 && ntc == 1) LAUNCH_DR(4, 1);
-      else if (ks == 8 && ntc == 2) LAUNCH_DR(8, 2);
-      else if (ks == 8 && ntc == 1) LAUNCH_DR(8, 1);
-      else LAUNCH_DR(4, 2);
-#undef LAUNCH_DR
+      auto launch = [&](auto kernel) {
+        fplx_launch(kernel, nb, 256, 0, st, (const bf16_t*)x, ldx, (const bf16_t*)wf, bias, (bf16_t*)y, ldy, n, d, h, w, fplx_xcd_on());
+      };
+      if (ks == 4 && ntc == 1) launch(deconv_fwd_rows<4, 1>);
+      else if (ks == 8 && ntc == 2) launch(deconv_fwd_rows<8, 2>);
+      else if (ks == 8 && ntc == 1) launch(deconv_fwd_rows<8, 1>);
+      else launch(deconv_fwd_rows<4, 2>);
       int rc = fplx_check_launch("mfma_deconv2_fwd_rows");
       return rc < 0 ? rc : 1;
     }
@@ -2589,21 +2555,15 @@ extern "C" int fplx_mfma_deconv2_dgrad(const void* dy, int64_t ldy, const void* 
     int rcs = fplx_check_launch("mfma_deconv2_dgrad_small");
     return rcs < 0 ? rcs : 1;
   }
-#define LAUNCH_DD(MT_, NTL_, MODE_, GRID_)                                                                          \
-  conv_fwd_direct<MT_, NTL_, MODE_><<<GRID_, DIRECT_THREADS, 0, st>>>((const bf16_t*)dy, ldy, (const bf16_t*)wb, nullptr, \
-                                                                      (bf16_t*)dx, ldx, n, d, h, w, cout, cin, nullptr)
-  if (cin % 64 == 0) {
-    dim3 grid((unsigned)((V + 255) / 256), cin / 64);
-    if ((int64_t)grid.x * grid.y < 192) {                     // deep levels: 128-voxel blocks, twice as many of them
-      dim3 g1((unsigned)((V + 127) / 128), cin / 64);
-      if (sd == 2) LAUNCH_DD(1, 2, 1, g1); else LAUNCH_DD(1, 2, 2, g1);
-    } else if (sd == 2) LAUNCH_DD(2, 2, 1, grid);
-    else LAUNCH_DD(2, 2, 2, grid);
-  } else {
-    dim3 grid((unsigned)((V + 511) / 512), cin / 32);
-    if (sd == 2) LAUNCH_DD(4, 1, 1, grid); else LAUNCH_DD(4, 1, 2, grid);
-  }
-#undef LAUNCH_DD
+  // the direct kernel as a data gradient (MODE 1: 8 taps, 2: the 4 in-plane taps): dy is its input, Cout its K dimension
+  const bool wide = cin % 64 == 0;
+  const dim3 grid = wide ? dim3((unsigned)((V + 255) / 256), cin / 64) : dim3((unsigned)((V + 511) / 512), cin / 32);
+  const bool deep = wide && (int64_t)grid.x * grid.y < 192;   // deep levels: 128-voxel blocks, twice as many of them
+  const auto k = deep ? (sd == 2 ? conv_fwd_direct<1, 2, 1> : conv_fwd_direct<1, 2, 2>)
+                 : wide ? (sd == 2 ? conv_fwd_direct<2, 2, 1> : conv_fwd_direct<2, 2, 2>)
+                        : (sd == 2 ? conv_fwd_direct<4, 1, 1> : conv_fwd_direct<4, 1, 2>);
+  fplx_launch(k, deep ? dim3((unsigned)((V + 127) / 128), cin / 64) : grid, DIRECT_THREADS, 0, st, (const bf16_t*)dy, ldy,
+              (const bf16_t*)wb, nullptr, (bf16_t*)dx, ldx, n, d, h, w, cout, cin, nullptr, nullptr);
   int rc = fplx_check_launch("mfma_deconv2_dgrad");
   return rc < 0 ? rc : 1;
 }
@@ -2620,19 +2580,15 @@ extern "C" int fplx_mfma_deconv2_wgrad(const void* x, int64_t ldx, const void* d
     return 0;
   const DwCfg c = dw_cfg(n, d, h, w, cin, cout);
   if (ws_bytes < c.ws) return fplx_fail(FPLX_E_WORKSPACE, "mfma_deconv2_wgrad: workspace %zu < %zu", ws_bytes, c.ws);
-  dim3 grid(c.nblk, c.npairs);
   const size_t lds = (size_t)(c.cit + 8) * 128 * 64;
   float* bpart = db ? (float*)((char*)ws + (size_t)c.nblk * c.npairs * 8 * c.cit * 1024 * sizeof(float)) : nullptr;
-#define LAUNCH_DW(CIT)                                                                                              \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)deconv_wgrad_mfma<CIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    deconv_wgrad_mfma<CIT><<<grid, 256, lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, bpart, n, d, \
-                                                   h, w, cin, cout, sd);                                            \
-  } while (0)
-  if (c.cit == 4) LAUNCH_DW(4);
-  else if (c.cit == 2) LAUNCH_DW(2);
-  else LAUNCH_DW(1);
-#undef LAUNCH_DW
+  auto launch = [&](auto kernel) {
+    fplx_launch(kernel, dim3(c.nblk, c.npairs), 256, lds, st, (const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, bpart, n, d,
+                h, w, cin, cout, sd);
+  };
+  if (c.cit == 4) launch(deconv_wgrad_mfma<4>);
+  else if (c.cit == 2) launch(deconv_wgrad_mfma<2>);
+  else launch(deconv_wgrad_mfma<1>);
   const int64_t total = (int64_t)c.npairs * 8 * c.cit * 1024;
   if (db) deconv_bias_reduce<<<cout, 64, 0, st>>>(bpart, c.nblk, cout, db);
   deconv_wgrad_reduce<<<(unsigned)((total + 63) / 64), 256, 0, st>>>((const float*)ws, c.nblk, c.npairs, c.cit, cin, cout, dw,

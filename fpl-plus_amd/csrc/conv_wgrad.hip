@@ -19,13 +19,10 @@
 //   * LDS-DMA staging through buffer descriptors (buffer_load_dwordx4 ... offen lds): halo, padding and ragged footprints are
 //     the hardware's out-of-range zeros, the per-lane offsets are constants of the march, the depth is the scalar offset;
 //     no staging registers, no commit phase, a 4-slot x ring + 2-slot dy ring.
-#include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Wint-to-pointer-cast"      // LDS pointers are 32 bits wide: they are formed from 32-bit addresses
-
-extern "C" int fplx_wgrad_reduce_launch(const float* part, int nblk, int npairs, int cin, int cout, float* dw, int mid,
-                                        hipStream_t st);      // conv_mfma.hip
 
 namespace {
 
@@ -737,14 +734,17 @@ inline RollCfg roll_cfg(int n, int d, int h, int w, int cin, int cout, bool twod
 
 }  // namespace
 
-// 1 if the rolling-window kernel takes the layer (3D, both channel counts multiples of 32, a sample below 1 GiB so that the
-// out-of-range marker 0x40000000 cannot alias a voxel)
-extern "C" int fplx_wgroll_ok(int n, int d, int h, int w, int cin, int cout, int64_t ldx, int64_t ldy) {
+// 1 if the rolling-window kernel takes the layer: both channel counts multiples of 32, a sample below 1 GiB so that the
+// out-of-range marker 0x40000000 cannot alias a voxel (tested here for the smallest leading dimensions, ldx = cin and
+// ldy = cout: the launcher repeats it for the operands' own), the 2D form enabled, a split x only as 2 x 32 channels
+extern "C" int fplx_wgroll_ok(int n, int d, int h, int w, int cin, int cout, int mid, int splitx) {
   if (!fplx_knob(FPLX_K_WG_ROLL)) return 0;
   if (cin % 32 != 0 || cout % 32 != 0) return 0;
   if ((int64_t)d * h * w < fplx_knob(FPLX_K_WG_ROLL_MINVOX)) return 0;
   if (h < 8 || w < 16) return 0;
-  if ((int64_t)d * h * w * ldx * 2 > ((int64_t)1 << 30) || (int64_t)d * h * w * ldy * 2 > ((int64_t)1 << 30)) return 0;
+  if ((int64_t)d * h * w * cin * 2 > ((int64_t)1 << 30) || (int64_t)d * h * w * cout * 2 > ((int64_t)1 << 30)) return 0;
+  if (mid && !fplx_knob(FPLX_K_WG_ROLL2D)) return 0;
+  if (splitx && cin != 64) return 0;
   return 1;
 }
 
@@ -753,58 +753,38 @@ extern "C" size_t fplx_wgroll_ws_bytes(int n, int d, int h, int w, int cin, int 
   return a > b ? a : b;
 }
 
-// returns 1 if launched, 0 if not applicable, < 0 on error.  dw fp32 [Cout][Cin][27]; x1: second ci tile of a split Cin = 64
+// for a layer fplx_wgroll_ok accepts (the weight-gradient plan of conv_mfma.hip has asked): returns 1 if launched, 0 if the
+// operands are not the kernel's (alignment, a sample of more than 1 GiB in ldx / ldy), < 0 on error.
+// dw fp32 [Cout][Cin][27]; x1: second ci tile of a split Cin = 64
 // mid != 0: a Conv2d per depth slice (conv_wgrad_roll2d), dw fp32 [Cout][Cin][3][3]
 extern "C" int fplx_wgroll_conv3d_wgrad(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, int n, int d, int h,
                                         int w, int cin, int cout, void* ws, size_t ws_bytes, hipStream_t st, const void* x1,
                                         int mid) {
-  if (!fplx_wgroll_ok(n, d, h, w, cin, cout, ldx, ldy)) return 0;
-  if (mid && !fplx_knob(FPLX_K_WG_ROLL2D)) return 0;
+  if ((int64_t)d * h * w * ldx * 2 > ((int64_t)1 << 30) || (int64_t)d * h * w * ldy * 2 > ((int64_t)1 << 30)) return 0;
   if (ldx % 8 != 0 || ldy % 8 != 0 || ((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)x1 % 16)) return 0;
-  if (x1 && cin != 64) return 0;
   const RollCfg c = roll_cfg(n, d, h, w, cin, cout, mid != 0);
   if (ws_bytes < c.ws) return fplx_fail(FPLX_E_WORKSPACE, "wgroll_conv3d_wgrad: workspace %zu < %zu", ws_bytes, c.ws);
-  dim3 grid(c.nblk, c.npairs);
-  if (mid) {
-#define LAUNCH_ROLL2D(TH_, TW_)                                                                                     \
-  do {                                                                                                              \
-    using G_ = WR2<TH_, TW_>;                                                                                       \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_roll2d<TH_, TW_>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-    conv_wgrad_roll2d<TH_, TW_><<<grid, 256, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, d, h, w, cin, \
-                                                           cout, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on()); \
-  } while (0)
-    if (c.th == 16) LAUNCH_ROLL2D(16, 16); else if (c.tw == 32) LAUNCH_ROLL2D(8, 32); else LAUNCH_ROLL2D(8, 16);
-#undef LAUNCH_ROLL2D
-    int rc2 = fplx_check_launch("wgroll_conv2d_wgrad");
-    if (rc2 < 0) return rc2;
-    rc2 = fplx_wgrad_reduce_launch((const float*)ws, c.nblk, c.npairs, cin, cout, dw, 1, st);
-    return rc2 < 0 ? rc2 : 1;
-  }
-#define LAUNCH_ROLL(TH_, TW_, MB_)                                                                                   \
-  do {                                                                                                              \
-    using G_ = WR<TH_, TW_, MB_>;                                                                                   \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_roll<TH_, TW_, MB_>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-    conv_wgrad_roll<TH_, TW_, MB_><<<grid, 256, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, d, h, w, \
-                                                              cin, cout, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, \
-                                                              fplx_xcd_on());                                       \
-  } while (0)
-#define LAUNCH_ROLL16(MB_)                                                                                          \
-  do {                                                                                                              \
-    using G_ = WR16<8, MB_>;                                                                                        \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_roll16<8, MB_>, hipFuncAttributeMaxDynamicSharedMemorySize, G_::LDS); \
-    conv_wgrad_roll16<8, MB_><<<grid, 256, G_::LDS, st>>>((const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, d, h, w, cin, \
-                                                         cout, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on()); \
-  } while (0)
   // mb: the mid-step barrier form (5 + 3 ring slots); the 8 x 16 footprint keeps the 4 + 2 rings (two blocks per CU) unless mb = 2
   const int mb = (int)fplx_knob(FPLX_K_WG_ROLL_MB);
-  if (c.th == 8 && c.tw == 32 && fplx_knob(FPLX_K_WG_ROLL_M16)) { if (mb) LAUNCH_ROLL16(true); else LAUNCH_ROLL16(false); }
-  else if (c.th == 16) { if (mb) LAUNCH_ROLL(16, 16, true); else LAUNCH_ROLL(16, 16, false); }
-  else if (c.tw == 32) { if (mb) LAUNCH_ROLL(8, 32, true); else LAUNCH_ROLL(8, 32, false); }
-  else { if (mb == 2) LAUNCH_ROLL(8, 16, true); else LAUNCH_ROLL(8, 16, false); }
-#undef LAUNCH_ROLL16
-#undef LAUNCH_ROLL
-  int rc = fplx_check_launch("wgroll_conv3d_wgrad");
+  auto launch = [&](auto kernel, int lds) {
+    fplx_launch(kernel, dim3(c.nblk, c.npairs), 256, lds, st, (const bf16_t*)x, ldx, (const bf16_t*)dy, ldy, (float*)ws, d, h, w, cin,
+                cout, c.tilesH, c.tilesW, c.dsegs, c.dlen, (const bf16_t*)x1, fplx_xcd_on());
+  };
+  if (mid) {
+    if (c.th == 16) launch(conv_wgrad_roll2d<16, 16>, WR2<16, 16>::LDS);
+    else if (c.tw == 32) launch(conv_wgrad_roll2d<8, 32>, WR2<8, 32>::LDS);
+    else launch(conv_wgrad_roll2d<8, 16>, WR2<8, 16>::LDS);
+  } else if (c.th == 8 && c.tw == 32 && fplx_knob(FPLX_K_WG_ROLL_M16)) {
+    if (mb) launch(conv_wgrad_roll16<8, true>, WR16<8, true>::LDS); else launch(conv_wgrad_roll16<8, false>, WR16<8, false>::LDS);
+  } else if (c.th == 16) {
+    if (mb) launch(conv_wgrad_roll<16, 16, true>, WR<16, 16, true>::LDS); else launch(conv_wgrad_roll<16, 16, false>, WR<16, 16, false>::LDS);
+  } else if (c.tw == 32) {
+    if (mb) launch(conv_wgrad_roll<8, 32, true>, WR<8, 32, true>::LDS); else launch(conv_wgrad_roll<8, 32, false>, WR<8, 32, false>::LDS);
+  } else {
+    if (mb == 2) launch(conv_wgrad_roll<8, 16, true>, WR<8, 16, true>::LDS); else launch(conv_wgrad_roll<8, 16, false>, WR<8, 16, false>::LDS);
+  }
+  int rc = fplx_check_launch(mid ? "wgroll_conv2d_wgrad" : "wgroll_conv3d_wgrad");
   if (rc < 0) return rc;
-  rc = fplx_wgrad_reduce_launch((const float*)ws, c.nblk, c.npairs, cin, cout, dw, 0, st);
+  rc = fplx_wgrad_reduce_launch((const float*)ws, c.nblk, c.npairs, cin, cout, dw, mid ? 1 : 0, st);
   return rc < 0 ? rc : 1;
 }

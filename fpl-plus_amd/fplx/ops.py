@@ -134,9 +134,6 @@ def conv3d_stats_rows(dims, cin, cout, k, x_dt, y_dt, mid=False):
     return _lib.lib().fplx_conv3d_stats_rows(n, d, h, w, cin, cout, k[0], k[1], k[2], x_dt, y_dt)
 
 
-_fwd_ws = {}
-
-
 def conv3d_fwd_ws_bytes(dims, cin, cout, k, x_dt, y_dt, mid=False):
     n, d, h, w = dims
     if mid:
@@ -144,17 +141,24 @@ def conv3d_fwd_ws_bytes(dims, cin, cout, k, x_dt, y_dt, mid=False):
     return _lib.lib().fplx_conv3d_fwd_ws_bytes(n, d, h, w, cin, cout, k[0], k[1], k[2], x_dt, y_dt)
 
 
+_fwd_ws = {}
+
+
+def _fwd_scratch(need, device):
+    """scratch of `need` bytes for the split-K forward kernels (None for 0), per (device, stream): launches on one stream are
+    ordered and may share it, launches on different streams (the engine runs two) may not"""
+    if not need:
+        return None
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    if key not in _fwd_ws or _fwd_ws[key].numel() < need:
+        _fwd_ws[key] = torch.empty(int(need), dtype=torch.uint8, device=device)
+    return _fwd_ws[key]
+
+
 def conv3d_fwd(x, xs, x_dt, wp, bias, y, ys, y_dt, dims, cin, cout, k, stats=None, ws=None, mid=False):
     n, d, h, w = dims
     if ws is None:
-        need = conv3d_fwd_ws_bytes(dims, cin, cout, k, x_dt, y_dt, mid)
-        if need:
-            # scratch for the split-K kernels, per (device, stream): launches on one stream are ordered and may share it,
-            # launches on different streams (the engine runs two) may not
-            key = (y.device, torch.cuda.current_stream(y.device).cuda_stream)
-            if key not in _fwd_ws or _fwd_ws[key].numel() < need:
-                _fwd_ws[key] = torch.empty(int(need), dtype=torch.uint8, device=y.device)
-            ws = _fwd_ws[key]
+        ws = _fwd_scratch(conv3d_fwd_ws_bytes(dims, cin, cout, k, x_dt, y_dt, mid), y.device)
     nws = 0 if ws is None else ws.numel() * ws.element_size()
     if mid:
         assert tuple(k) == (3, 3, 3)
@@ -229,13 +233,7 @@ def conv3d_fwd_act(x0, x1, wp, bias, slope, y, dims, cin, cout, mid=False, n_x0=
     """inference: y = PReLU(conv(x; wp) + bias) with the eval-mode BatchNorm already folded into wp / bias; x1: the second half
     of a channel concatenation (or None); n_x0: x0 holds that many samples, read modulo (0 = all).  bf16 NDHWC 2-D views."""
     n, d, h, w = dims
-    ws = None
-    need = conv3d_fwd_ws_bytes(dims, cin, cout, (3, 3, 3), BF16, BF16, mid)
-    if need:
-        key = (y.device, torch.cuda.current_stream(y.device).cuda_stream)
-        if key not in _fwd_ws or _fwd_ws[key].numel() < need:
-            _fwd_ws[key] = torch.empty(int(need), dtype=torch.uint8, device=y.device)
-        ws = _fwd_ws[key]
+    ws = _fwd_scratch(conv3d_fwd_ws_bytes(dims, cin, cout, (3, 3, 3), BF16, BF16, mid), y.device)
     if x1 is not None:
         assert ld_of(x0) == ld_of(x1)
     call("fplx_conv3d_fwd_act", ptr(x0), ptr(x1), ld_of(x0), ptr(wp), ptr(bias), ptr(slope), ptr(y), ld_of(y), n, d, h, w, cin,

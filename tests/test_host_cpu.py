@@ -314,3 +314,27 @@ def test_late_import_warns_about_the_runtime_environment():
     assert out.startswith("0 ") and "('4', 'preset')" in out and "('0', 'preset')" in out
     out = run(False, {})                                             # imported in time: set by fplx, no warning
     assert out.startswith("0 ") and "('8', 'fplx')" in out and "('1', 'fplx')" in out
+
+
+def test_dispatch_plan_matches_parent(golden_dir):
+    """every host query of the convolution dispatch (kernel family, geometry, split, statistics rows, workspace bytes, the
+    activation / concatenation forms) answers what the commit before the one-plan-per-path refactor answered: the grid of
+    tests/golden/make_golden_dispatch.py under each of its knob settings, integer for integer.  Pure host code, no launch."""
+    import make_golden_dispatch as mg
+    from fplx import _lib
+    doc = json.load(open(os.path.join(golden_dir, "dispatch_plan.json")))
+    assert doc["volumes"] == [list(v) for v in mg.VOLUMES] and doc["channels"] == [list(c) for c in mg.CHANNELS]
+    assert doc["columns"] == mg.COLUMNS and doc["knobs"] == [mg.knob_key(k) for k in mg.KNOBS]
+    want_all = mg.expand(doc)                    # the default rows + the recorded changes per knob setting: every row in full
+    kcols = [i for i, c in enumerate(mg.COLUMNS) if c.endswith(".kernel")]
+    seen = {r[i] for rows in want_all.values() for r in rows for i in kcols}
+    assert seen == set(range(8)), seen           # every FPLX_KERNEL_* is pinned somewhere: the grid must not shrink below that
+    defaults = {k: _lib.get_tuning(k) for k in _lib.tuning_keys()}
+    got = mg.replay(_lib)                        # restores each knob it flips from fplx_get_tuning, in a finally
+    assert {k: _lib.get_tuning(k) for k in defaults} == defaults
+    grid = mg.grid()
+    assert list(want_all) == list(got)
+    for kn, want in want_all.items():
+        assert len(want) == len(grid) == len(got[kn])
+        for g, a, b in zip(grid, got[kn], want):
+            assert a == b, (kn, g, [(c, x, y) for c, x, y in zip(mg.COLUMNS, a, b) if x != y])
