@@ -710,12 +710,15 @@ def pad_reflect(x, lower, out_size):
     return y
 
 
-def crop_flip(x, crop_min, out_size, flip_mask=0):
-    """crop box [crop_min, crop_min + out_size) of a [C,D,H,W] volume, then flip (bit0 W, bit1 H, bit2 D)"""
+def crop_flip(x, crop_min, out_size, flip_mask=0, out=None):
+    """crop box [crop_min, crop_min + out_size) of a [C,D,H,W] volume, then flip (bit0 W, bit1 H, bit2 D); out: an
+    existing contiguous [C,*out_size] destination of x's dtype"""
     require_gpu(x)
     assert x.dim() == 4 and x.is_contiguous()
     c, d, h, w = x.shape
-    y = torch.empty((c,) + tuple(out_size), dtype=x.dtype, device=x.device)
+    if out is not None:
+        assert out.is_cuda and out.is_contiguous() and out.dtype == x.dtype and tuple(out.shape) == (c,) + tuple(out_size)
+    y = torch.empty((c,) + tuple(out_size), dtype=x.dtype, device=x.device) if out is None else out
     call("fplx_crop_flip", ptr(x), ptr(y), _elem_bytes(x), c, d, h, w, crop_min[0], crop_min[1], crop_min[2], out_size[0],
          out_size[1], out_size[2], int(flip_mask), stream())
     return y
@@ -750,6 +753,74 @@ def label_bbox(label, mask_labels):
     call("fplx_label_bbox", ptr(label), c, d, h, w, ptr(ml), ml.numel(), ptr(out), stream())
     o = out.tolist()
     return o[0], o[1:5], o[5:9]
+
+
+def nonzero_bbox(x):
+    """-> (count, bb_min[4], bb_max[4]) of {x != 0} on a float32 [C,D,H,W] volume, numpy.nonzero's test (a NaN counts, -0.0
+    does not); one device->host copy.  count == 0: bb_min / bb_max are meaningless"""
+    require_gpu(x)
+    if not (x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("fplx: nonzero_bbox takes a contiguous float32 [C,D,H,W] volume")
+    c, d, h, w = x.shape
+    out = torch.empty(9, dtype=torch.int32, device=x.device)
+    call("fplx_nonzero_bbox", ptr(x), c, d, h, w, ptr(out), stream())
+    o = out.tolist()
+    return o[0], o[1:5], o[5:9]
+
+
+def label_lut_table(source_list, target_list):
+    """the 256-entry table of convert_label (util/image_process.py:194-208) on uint8 labels: lut[v] = sum of the targets of
+    every source equal to v, mod 256 - a source listed twice adds its targets and wraps, labels not listed map to 0"""
+    if len(source_list) != len(target_list):
+        raise ValueError("fplx: label conversion takes as many targets as sources")
+    lut = [0] * 256
+    for s, t in zip(source_list, target_list):
+        if not (isinstance(s, (int, np.integer)) and isinstance(t, (int, np.integer)) and 0 <= s <= 255 and 0 <= t <= 255):
+            raise ValueError("fplx: label conversion takes integer labels in 0..255, got {0!r} -> {1!r}".format(s, t))
+        lut[int(s)] = (lut[int(s)] + int(t)) % 256
+    return lut
+
+
+def label_lut(label, lut, out=None):
+    """out = lut[label] on a uint8 volume of any shape; lut: 256 integers in 0..255 (a list, or a uint8 device tensor)"""
+    require_gpu(label)
+    if not (label.dtype == torch.uint8 and label.is_contiguous() and label.numel() > 0):
+        raise ValueError("fplx: label_lut takes a non-empty contiguous uint8 volume")
+    if not torch.is_tensor(lut):
+        lut = torch.tensor([int(v) for v in lut], dtype=torch.uint8, device=label.device)
+    require_gpu(lut)
+    if not (lut.dtype == torch.uint8 and lut.numel() == 256 and lut.is_contiguous()):
+        raise ValueError("fplx: label_lut takes a table of 256 uint8 entries")
+    out = torch.empty_like(label) if out is None else out
+    call("fplx_label_lut", ptr(label), ptr(out), label.numel(), ptr(lut), stream())
+    return out
+
+
+def partial_label_to_probability(label, class_num):
+    """uint8 label [D,H,W] (or any shape) with `class_num` marking unlabelled voxels -> (fp32 one-hot [class_num, *shape],
+    fp32 weight [*shape] = 1 - (label == class_num), largest label as a python int: one device->host copy)"""
+    require_gpu(label)
+    if not (label.dtype == torch.uint8 and label.is_contiguous() and label.numel() > 0):
+        raise ValueError("fplx: partial_label_to_probability takes a non-empty contiguous uint8 volume")
+    prob = torch.empty((class_num,) + tuple(label.shape), dtype=torch.float32, device=label.device)
+    weight = torch.empty(tuple(label.shape), dtype=torch.float32, device=label.device)
+    top = torch.empty(1, dtype=torch.int32, device=label.device)
+    call("fplx_partial_label_to_probability", ptr(label), ptr(prob), ptr(weight), int(class_num), label.numel(), ptr(top),
+         stream())
+    return prob, weight, int(top.item())
+
+
+def paste_roi(sub, lower, out_size):
+    """zeros of [C,*out_size] with the [C,d,h,w] volume `sub` at `lower`: the inverse of a crop, every element written once"""
+    require_gpu(sub)
+    if not (sub.dim() == 4 and sub.is_contiguous()):
+        raise ValueError("fplx: paste_roi takes a contiguous [C,D,H,W] volume")
+    c, sd, sh, sw = sub.shape
+    od, oh, ow = (int(v) for v in out_size)
+    out = torch.empty((c, max(od, 0), max(oh, 0), max(ow, 0)), dtype=sub.dtype, device=sub.device)
+    call("fplx_paste_roi", ptr(sub), ptr(out), _elem_bytes(sub), c, sd, sh, sw, od, oh, ow, int(lower[0]), int(lower[1]),
+         int(lower[2]), stream())
+    return out
 
 
 def label_to_probability(label, class_num):

@@ -3,12 +3,15 @@
 Mirrors the classes FPL+'s configs name (config_dual/data_vs/vs_t1s_g.cfg:21-23:
 train_transform = [NormalizeWithMeanStd, Pad, RandomCrop, RandomFlip, LabelToProbability]) and the geometric augmentation
 a user of the reference adds first (RandomRotate, Rescale, RandomRescale: rotate.py, rescale.py) and the intensity family
-(min-max / percentile normalisation, thresholding, gamma correction, Gaussian noise: normalize.py, threshold.py, intensity.py):
+(min-max / percentile normalisation, thresholding, gamma correction, Gaussian noise: normalize.py, threshold.py, intensity.py)
+and the crop, bounding-box and label family (CenterCrop, CropWithBoundingBox, RandomResizedCrop, LabelConvert,
+LabelConvertNonzero, PartialLabelToProbability, ReduceLabelDim, GrayscaleToRGB: crop.py, label_convert.py) - all 23 names of
+the reference's TransformDict:
 same class names, same lower-cased parameter keys (PyMIC/pymic/transform/*.py), same `__call__(sample) -> sample`
 contract and the same `<Name>_Param` json strings in the sample, so `TransformDict[name](params)` drops in for
 PyMIC/pymic/transform/trans_dict.py:42.  The difference is where the volumes live: `sample['image']` (float32
 [C,D,H,W]), `sample['label']` (uint8 [1,D,H,W]) and `sample['pixel_weight']` (float32 [1,D,H,W]) are device tensors
-and every gather / reduction / interpolation is a HIP kernel (csrc/sample.hip, csrc/resample.hip).  The random decisions
+and every gather / reduction / interpolation is a HIP kernel (csrc/sample.hip, csrc/resample.hip, csrc/intensity.hip, csrc/crop_label.hip).  The random decisions
 are drawn on the host from Python's `random` (RandomRotate: numpy's global generator) in exactly the reference's order,
 so a seeded run picks the same crops, flips, angles and ratios as the reference.
 """
@@ -131,9 +134,99 @@ class Pad(AbstractTransform):
         return sample
 
 
-class RandomCrop(AbstractTransform):
+def _check_tensor(t, name):
+    """the rank-free form of _check_volume, for the classes that also take 2-D samples [C,H,W]"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError("fplx.transform: sample['{0:}'] must be a device tensor".format(name))
+    return t.contiguous()
+
+
+class CenterCrop(AbstractTransform):
+    """crop.py:13-108.  centercrop_output_size [D, H, W] (D None: the depth is kept); lower corner int(margin / 2).  Crops
+    'image', 'label', 'pixel_weight' and 'image1'.  The inverse pastes a prediction (or each one of a list) back into
+    zeros of the recorded shape; CropWithBoundingBox, RandomCrop and RandomResizedCrop derive from this class as in the
+    reference, and the first two inherit the inverse.  An output size beyond the volume - the reference then slices from
+    a negative start and returns a strip from the far end - is refused."""
+    _name = 'CenterCrop'
+
+    def __init__(self, params):
+        super(CenterCrop, self).__init__(params)
+        self.output_size = params['centercrop_output_size']
+        self.inverse = params.get('centercrop_inverse', True)
+
+    def _get_crop_param(self, sample):
+        """-> sample (with the <Name>_Param string), lower corner [3], extent [3] of the block that is gathered"""
+        shape = list(sample['image'].shape)
+        assert len(self.output_size) == 3
+        size = list(self.output_size)
+        if size[0] is None:
+            size[0] = shape[1]
+        margin = [shape[i + 1] - size[i] for i in range(3)]
+        if min(margin) < 0:
+            raise ValueError("fplx.transform: CenterCrop output size {0:} exceeds the volume {1:}".format(size, shape[1:]))
+        crop_min = [int(m / 2) for m in margin]
+        crop_max = [crop_min[i] + size[i] for i in range(3)]
+        sample['CenterCrop_Param'] = json.dumps((shape, [0] + crop_min, shape[0:1] + crop_max))
+        return sample, crop_min, size
+
+    def __call__(self, sample):
+        image = _check_volume(sample['image'], 'image')
+        sample, crop_min, size = self._get_crop_param(sample)
+        sample['image'] = ops.crop_flip(image, crop_min, size)
+        for k in self._others(sample):
+            sample[k] = ops.crop_flip(_check_volume(sample[k], k), crop_min, size)
+        return sample
+
+    def inverse_transform_for_prediction(self, sample):
+        origin_shape, crop_min, _ = _json_param(sample[self._name + '_Param'])
+        # the block's extent is the prediction's own: a box that ran past the volume was truncated on the way in
+        return _on_prediction(sample, lambda p: ops.paste_roi(p, crop_min[1:], origin_shape[1:]))
+
+
+class CropWithBoundingBox(CenterCrop):
+    """crop.py:110-167.  The box of the image's non-zero voxels over all channels (numpy.nonzero: a NaN counts, -0.0 does
+    not) decides the crop: start None and output_size None -> the box itself; start None -> output_size centred on the
+    box, clamped at 0; both given -> start and output_size as they are.  A box past the volume is truncated as a numpy
+    slice is, while <Name>_Param keeps the untruncated numbers.  Refused: start with output_size None (the reference
+    fails on len(None)) and an all-zero image (the reference fails on the minimum of an empty array)."""
+    _name = 'CropWithBoundingBox'
+
+    def __init__(self, params):
+        self.start = params['cropwithboundingbox_start']
+        self.output_size = params['cropwithboundingbox_output_size']
+        self.inverse = params.get('cropwithboundingbox_inverse', True)
+        self.task = params['task']
+        if self.start is not None and self.output_size is None:
+            raise ValueError("fplx.transform: CropWithBoundingBox_start needs CropWithBoundingBox_output_size")
+
+    def _get_crop_param(self, sample):
+        image = sample['image']
+        shape = list(image.shape)
+        count, bb_min, bb_max = ops.nonzero_bbox(image)
+        if count == 0:
+            raise ValueError("fplx.transform: CropWithBoundingBox on an all-zero image")
+        bb_min, bb_max = bb_min[1:], bb_max[1:]
+        if self.start is None:
+            if self.output_size is None:
+                crop_min, crop_max = bb_min, bb_max
+            else:
+                assert len(self.output_size) == 3
+                crop_min = [int((bb_min[i] + bb_max[i] + 1) / 2) - int(self.output_size[i] / 2) for i in range(3)]
+                crop_min = [max(0, crop_min[i]) for i in range(3)]
+                crop_max = [crop_min[i] + self.output_size[i] for i in range(3)]
+        else:
+            assert len(self.start) == 3
+            crop_min = list(self.start)
+            crop_max = [crop_min[i] + self.output_size[i] for i in range(3)]
+        sample['CropWithBoundingBox_Param'] = json.dumps((shape, [0] + crop_min, shape[0:1] + crop_max))
+        size = [min(crop_max[i], shape[i + 1]) - crop_min[i] for i in range(3)]
+        return sample, crop_min, size
+
+
+class RandomCrop(CenterCrop):
     """crop.py:165-245.  Draw order: one randint per axis with a margin, then random() for the foreground focus,
-    then one randint per axis inside the label's bounding box."""
+    then one randint per axis inside the label's bounding box.  The inverse is CenterCrop's."""
+    _name = 'RandomCrop'
 
     def __init__(self, params):
         self.output_size = params['randomcrop_output_size']
@@ -166,13 +259,59 @@ class RandomCrop(AbstractTransform):
         sample['RandomCrop_Param'] = json.dumps((shape, [0] + crop_min, shape[0:1] + crop_max))
         return sample, crop_min, size
 
+
+class RandomResizedCrop(CenterCrop):
+    """crop.py:246-320, 2-D samples [C,H,W] only (the reference asserts it).  Draw order: random() for the scale, random()
+    for the aspect ratio, then one randint per axis.  The crop is zoomed to randomresizedcrop_output_size with
+    scipy.ndimage.zoom's rules (image and pixel weight order 1, label order 0) by ops.resample_affine on the plane as a
+    depth-1 volume; 'image1' is left alone and there is no inverse, as in the reference."""
+    _name = 'RandomResizedCrop'
+
+    def __init__(self, params):
+        self.output_size = params['randomresizedcrop_output_size']
+        self.scale = params['randomresizedcrop_scale']
+        self.ratio = params['randomresizedcrop_ratio']
+        self.inverse = params.get('randomresizedcrop_inverse', False)
+        self.task = params['task']
+        assert isinstance(self.output_size, (list, tuple))
+        assert isinstance(self.scale, (list, tuple))
+        assert isinstance(self.ratio, (list, tuple))
+
+    def _get_crop_param(self, sample):
+        shape = list(sample['image'].shape)
+        input_dim = len(shape) - 1
+        assert input_dim == 2
+        assert input_dim == len(self.output_size)
+        scale = self.scale[0] + random.random() * (self.scale[1] - self.scale[0])
+        ratio = self.ratio[0] + random.random() * (self.ratio[1] - self.ratio[0])
+        crop_w = shape[-1] * scale
+        crop_h = crop_w * ratio
+        crop_h = min(crop_h, shape[-2])
+        size = [int(crop_h), int(crop_w)]
+        margin = [shape[i + 1] - size[i] for i in range(2)]
+        crop_min = [random.randint(0, m) for m in margin]
+        crop_max = [crop_min[i] + size[i] for i in range(2)]
+        sample['RandomResizedCrop_Param'] = json.dumps((shape, [0] + crop_min, shape[0:1] + crop_max))
+        return sample, crop_min, size
+
     def __call__(self, sample):
-        image = _check_volume(sample['image'], 'image')
+        image = _check_tensor(sample['image'], 'image')
         sample, crop_min, size = self._get_crop_param(sample)
-        sample['image'] = ops.crop_flip(image, crop_min, size)
-        for k in self._others(sample):
-            sample[k] = ops.crop_flip(_check_volume(sample[k], k), crop_min, size)
+        zoom = [1.0] + [(self.output_size[i] + 0.0) / size[i] for i in range(2)]
+
+        def crop_zoom(t, order):                         # [C,H,W] -> [C,1,H,W] -> crop -> zoom -> [C,H',W']
+            crop = ops.crop_flip(t.unsqueeze(1), [0] + crop_min, [1] + size)
+            return _zoom(crop, zoom, _order_for(crop, order)).squeeze(1)
+
+        sample['image'] = crop_zoom(image, 1)
+        if 'label' in sample and self.task == 'segmentation':
+            sample['label'] = crop_zoom(_check_tensor(sample['label'], 'label'), 0)
+        if 'pixel_weight' in sample and self.task == 'segmentation':
+            sample['pixel_weight'] = crop_zoom(_check_tensor(sample['pixel_weight'], 'pixel_weight'), 1)
         return sample
+
+    def inverse_transform_for_prediction(self, sample):
+        raise ValueError("not implemented")
 
 
 class RandomFlip(AbstractTransform):
@@ -230,6 +369,97 @@ class LabelToProbability(AbstractTransform):
         if label.dtype != torch.uint8:
             raise ValueError("fplx.transform: sample['label'] must be uint8")
         sample['label_prob'] = ops.label_to_probability(label[0], self.class_num)
+        return sample
+
+
+def _check_label(sample):
+    label = _check_tensor(sample['label'], 'label')
+    if label.dtype != torch.uint8:
+        raise ValueError("fplx.transform: sample['label'] must be uint8")
+    return label
+
+
+class ReduceLabelDim(AbstractTransform):
+    """label_convert.py:13-25: the label loses its channel axis (a view; nothing is moved)"""
+
+    def __init__(self, params):
+        super(ReduceLabelDim, self).__init__(params)
+        self.inverse = params.get('reducelabeldim_inverse', False)
+
+    def __call__(self, sample):
+        sample['label'] = sample['label'][0]
+        return sample
+
+
+class LabelConvert(AbstractTransform):
+    """label_convert.py:27-50 on uint8 labels, one table look-up per voxel.  The table restates convert_label
+    (util/image_process.py:194-208): labels that are not listed become 0, a source listed twice adds its targets modulo
+    256.  Sources or targets outside 0..255 - an OverflowError or a silent no-match in the reference - are refused."""
+
+    def __init__(self, params):
+        super(LabelConvert, self).__init__(params)
+        self.source_list = params['labelconvert_source_list']
+        self.target_list = params['labelconvert_target_list']
+        self.inverse = params.get('labelconvert_inverse', False)
+        assert len(self.source_list) == len(self.target_list)
+        self._lut = ops.label_lut_table(self.source_list, self.target_list)
+
+    def __call__(self, sample):
+        sample['label'] = ops.label_lut(_check_label(sample), self._lut)
+        return sample
+
+
+class LabelConvertNonzero(AbstractTransform):
+    """label_convert.py:52-64: every nonzero label becomes 1 (the table 0, 1, 1, ...)"""
+
+    def __init__(self, params):
+        super(LabelConvertNonzero, self).__init__(params)
+        self.inverse = params.get('labelconvertnonzero_inverse', False)
+        self._lut = [0] + [1] * 255
+
+    def __call__(self, sample):
+        sample['label'] = ops.label_lut(_check_label(sample), self._lut)
+        return sample
+
+
+class PartialLabelToProbability(AbstractTransform):
+    """label_convert.py:97-130: labels 0 .. class_num - 1 are classes, class_num marks unlabelled voxels.  One pass writes
+    the one-hot 'label_prob' [class_num, ...] and 'pixel_weight' [1, ...] = 1 - (label == class_num), replacing a pixel
+    weight the sample had, and finds the largest label: beyond class_num it is the reference's AssertionError."""
+
+    def __init__(self, params):
+        super(PartialLabelToProbability, self).__init__(params)
+        self.class_num = params['partiallabeltoprobability_class_num']
+        self.inverse = params.get('partiallabeltoprobability_inverse', False)
+
+    def __call__(self, sample):
+        label = _check_label(sample)[0]
+        prob, weight, top = ops.partial_label_to_probability(label, self.class_num)
+        assert top <= self.class_num
+        sample['label_prob'] = prob
+        sample['pixel_weight'] = weight.unsqueeze(0)
+        return sample
+
+
+class GrayscaleToRGB(AbstractTransform):
+    """intensity.py:88-101 on [C,H,W] or [C,D,H,W]: one channel becomes three copies, three channels stay"""
+
+    def __init__(self, params):
+        super(GrayscaleToRGB, self).__init__(params)
+        self.inverse = params.get('grayscaletorgb_inverse', False)
+
+    def __call__(self, sample):
+        image = _check_tensor(sample['image'], 'image')
+        if image.dim() not in (3, 4):
+            raise ValueError("fplx.transform: sample['image'] must be a [C,H,W] or [C,D,H,W] device tensor")
+        assert image.shape[0] == 1 or image.shape[0] == 3
+        if image.shape[0] == 1:
+            size = ([1] * (4 - image.dim())) + list(image.shape[1:])
+            src = image.view(1, *size)
+            rgb = torch.empty([3] + size, dtype=image.dtype, device=image.device)
+            for k in range(3):
+                ops.crop_flip(src, (0, 0, 0), size, out=rgb[k:k + 1])
+            sample['image'] = rgb.view(3, *image.shape[1:])
         return sample
 
 
@@ -630,6 +860,14 @@ TransformDict = {
     'ChannelWiseThresholdWithNormalize': ChannelWiseThresholdWithNormalize,
     'GammaCorrection': GammaCorrection,
     'GaussianNoise': GaussianNoise,
+    'CenterCrop': CenterCrop,
+    'CropWithBoundingBox': CropWithBoundingBox,
+    'RandomResizedCrop': RandomResizedCrop,
+    'LabelConvert': LabelConvert,
+    'LabelConvertNonzero': LabelConvertNonzero,
+    'PartialLabelToProbability': PartialLabelToProbability,
+    'ReduceLabelDim': ReduceLabelDim,
+    'GrayscaleToRGB': GrayscaleToRGB,
 }
 
 

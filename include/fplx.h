@@ -457,6 +457,31 @@ int fplx_label_to_probability(const unsigned char* label, float* prob, int class
                               fplx_stream_t stream);
 int fplx_set_weight(float* pixel_weight, int64_t n, float image_weight, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ crop, bounding-box and label transforms (csrc/crop_label.hip)
+ * CenterCrop / CropWithBoundingBox and their inverse, LabelConvert / LabelConvertNonzero, PartialLabelToProbability
+ * (PyMIC/pymic/transform/crop.py:13-167, label_convert.py:27-130).  The forward crops gather with fplx_crop_flip.
+ *  nonzero_bbox: out9 = [count, min c,d,h,w, max+1 c,d,h,w] (the layout of fplx_label_bbox) of {x != 0} over a fp32 volume
+ *             [c][d][h][w], numpy.nonzero's test: every bit pattern but +0.0 and -0.0 counts (a NaN does, -0.0 does not).
+ *             Integer min / max / sum only: the result does not depend on the order of the blocks.  count == 0 leaves
+ *             min = INT_MAX, max = 0.  Fewer than 2^31 elements.
+ *  label_lut: out[i] = lut256[in[i]] (lut256: 256 bytes in DEVICE memory); out may be in.  The host builds the table with
+ *             convert_label's arithmetic (util/image_process.py:194-208): the sum of the targets of every matching source,
+ *             mod 256; labels that are not listed map to 0.
+ *  partial_label_to_probability: prob[k][v] = (label[v] == k) for k < class_num, weight[v] = 1 - (label[v] == class_num),
+ *             *max_label (device int) = the largest label (label_convert.py:122-130; the caller raises when it exceeds
+ *             class_num).
+ *  paste_roi: out [c][od][oh][ow] = 0 outside the box [lo, lo + s), sub [c][sd][sh][sw] inside: numpy.zeros +
+ *             set_ND_volume_roi_with_bounding_box_range (crop.py:83-108) with every element written exactly once;
+ *             elem_bytes 4 or 1; sub and out must not overlap.
+ * Refused before any launch: FPLX_E_NULL, FPLX_E_BADSHAPE (non-positive extent, box outside the output, class_num outside
+ * 1..255), FPLX_E_BADDTYPE (element size). */
+int fplx_nonzero_bbox(const float* x, int c, int d, int h, int w, int* out9, fplx_stream_t stream);
+int fplx_label_lut(const uint8_t* in, uint8_t* out, int64_t n, const uint8_t* lut256, fplx_stream_t stream);
+int fplx_partial_label_to_probability(const uint8_t* label, float* prob, float* weight, int class_num, int64_t voxels,
+                                      int* max_label, fplx_stream_t stream);
+int fplx_paste_roi(const void* sub, void* out, int elem_bytes, int c, int sd, int sh, int sw, int od, int oh, int ow,
+                   int lo_d, int lo_h, int lo_w, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ geometric augmentation: affine resampling
  * RandomRotate / Rescale / RandomRescale (PyMIC/pymic/transform/rotate.py:14-92, rescale.py:14-153), which the reference
  * runs as scipy.ndimage.rotate / scipy.ndimage.zoom on the host.  y[ch][o] = interp(x[ch], M o + t) for x [c][d][h][w]
