@@ -18,6 +18,7 @@
 //     (L >> 2) & 3; the lane -> voxel map of an M-tile follows ds_read_b128's lane groups so that each group touches
 //     16 distinct 16-byte slots for every tap shift (rows 0, 2 in one group, rows 1, 3 in the other).
 #include "internal.h"
+#include "gfx950.h"
 #include <type_traits>
 
 #ifdef FPLX_STAMP
@@ -25,12 +26,6 @@ __device__ long long* fplx_brick_stamp_buf;      // set by tools/micro/brick_ben
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 struct BK {
   static constexpr int TW = 8, KC = 32, ROWB = 64, SWP = 12, THREADS = 256;
@@ -127,7 +122,6 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
   if (tr.first >= tr.end) return;
   const int c_lo = (int)((int64_t)(Cin / G::KC) * bz / gridDim.z);
   const int nch = (int)((int64_t)(Cin / G::KC) * (bz + 1) / gridDim.z) - c_lo;
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
   struct BrickPos { int n, d0, h0, w0; };
   auto position = [&](int64_t tile, BrickPos& B) {
@@ -144,18 +138,10 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
   if (loader) {
     // ================================================================ loader waves
     const int64_t xsample = (int64_t)D * H * W * ldx * 2;
-    u32x4 rw;
-    rw[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)wp);
-    rw[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)wp >> 32) & 0xFFFFu);
-    rw[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)27 * Cout * Cin * 2));
-    rw[3] = 0x00020000u;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
+    const u32x4 rw = buffer_rsrc(wp, (int64_t)27 * Cout * Cin * 2);
+    const unsigned lds0 = lds_addr(smem);
     auto buf_dma = [&](const u32x4& rsrc, unsigned vo, unsigned so, unsigned dst_off) {
-      const unsigned dst = lds0 + dst_off;
-      const unsigned so_ = __builtin_amdgcn_readfirstlane(so);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so_), "s"(dst) : "memory");
+      lds_dma_buffer(rsrc, vo, __builtin_amdgcn_readfirstlane(so), lds0 + dst_off);
     };
     // A brick's DMA lane offsets are NOT tabulated per brick (the round-2 kernel's setup(): 12 pieces x 64-bit address arithmetic,
     // about 5 K cycles per brick in front of its first stage - 18 % of a level-1 launch by the stamps): a lane's offset is
@@ -201,10 +187,7 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
         else xn = reinterpret_cast<const char*>(x) + (int64_t)B.n0 * xsample;
       }
       BrickSrc rs;
-      rs.rx[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
-      rs.rx[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
-      rs.rx[2] = __builtin_amdgcn_readfirstlane((unsigned)xsample);
-      rs.rx[3] = 0x00020000u;
+      rs.rx = buffer_rsrc(xn, xsample);
       rs.so = __builtin_amdgcn_readfirstlane(on ? (unsigned)(c * G::KC * 2) : 0x40000000u);
       return rs;
     };
@@ -233,8 +216,8 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
         for (int k = 0; k < G::NPW; ++k) weight_piece(0, 1, 1, k, true);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    block_sync();                                              // P0
+    wait_vmcnt0();
+    lds_barrier();                                             // P0
     int cc = 0, ws = 0;
     bool first_brick = true;
 #ifdef FPLX_STAMP
@@ -270,8 +253,8 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
           // the brick slot of the next chunk doubles as the previous brick's write-out staging: wait for the compute waves
           // (their statistics tail has a barrier of its own in front of that one; this brick's first weights are on their way)
           if (t9 == 0 && ch == 0 && !first_brick) {
-            if (STATS && stats) block_sync();
-            block_sync();
+            if (STATS && stats) lds_barrier();
+            lds_barrier();
           }
           const int nbp = 2 * t9 + 1 < G::NPB ? 2 : (2 * t9 < G::NPB ? 1 : 0);
           if (nbp > 0) {
@@ -283,28 +266,16 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
           STAMP(st_h1);
           // three slots: what was issued before this iteration has landed (this iteration's NPW + nbp pieces may fly on);
           // two slots: everything has
-          if (G::NWS == 3) {
-            const int nps = G::NPW + nbp;
-            if (nps == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else if (nps == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (nps == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else if (nps == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if (nps == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else if (nps == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if (nps == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else if (nps == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
+          if (G::NWS == 3) wait_vmcnt_upto8(G::NPW + nbp);
+          else wait_vmcnt0();
           STAMP(st_wait);
-          block_sync();                                        // the stage's barrier
+          lds_barrier();                                       // the stage's barrier
           STAMP(st_bar);
           ws = s1;
         }
       }
       if (!has_next) {
-        if (STATS && stats) block_sync();                      // the compute waves' statistics tail has one
+        if (STATS && stats) lds_barrier();                     // the compute waves' statistics tail has one
         break;
       }
       first_brick = false;
@@ -335,21 +306,21 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
   position(tile, cur);
   nxt = cur;
   if (tid < G::NT) bias_s[tid] = bias ? bias[n0 + tid] : 0.f;
-  block_sync();                                                // P0
+  lds_barrier();                                               // P0
 
   const int L0 = (hhalf * 4 + bk_row(r)) * G::SWP + bk_col(r);
   const int bb = (wn * (32 * NTW) + r) * G::ROWB + ((khalf ^ ((r >> 2) & 3)) << 4);
   bf16x8 fa[2][G::SD], fb[2][3 * NTW];
   auto load_a = [&](const char* brick, int kh, int kw, int ks, int buf) {
     int a0 = L0 + kh * G::SWP + kw;
-    asm volatile("" : "+v"(a0));
+    opaque_v(a0);
     const char* p = brick + a0 * G::ROWB + (((2 * ks + khalf) ^ ((a0 >> 2) & 3)) << 4);
 #pragma unroll
     for (int q = 0; q < G::SD; ++q) fa[buf][q] = *reinterpret_cast<const bf16x8*>(p + q * G::PL * G::ROWB);
   };
   auto load_b = [&](const char* wslot, int ks, int buf) {
     int b0 = bb;
-    asm volatile("" : "+v"(b0));
+    opaque_v(b0);
     const char* p = wslot + (b0 ^ (ks << 5));
 #pragma unroll
     for (int kd = 0; kd < 3; ++kd)
@@ -389,10 +360,10 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
         auto half = [&](int hf, const char* abrick, int akh, int akw, int aks, const char* bslot, int bks) {
           constexpr int NL = G::SD + 3 * NTW, M1 = G::M1;
           int a0 = L0 + akh * G::SWP + akw;
-          asm volatile("" : "+v"(a0));
+          opaque_v(a0);
           const char* pa = abrick + a0 * G::ROWB + (((2 * aks + khalf) ^ ((a0 >> 2) & 3)) << 4);
           int b0 = bb;
-          asm volatile("" : "+v"(b0));
+          opaque_v(b0);
           const char* pb = bslot + (b0 ^ (bks << 5));
           auto load = [&](int li) {
             if (li < G::SD) fa[hf ^ 1][li] = *reinterpret_cast<const bf16x8*>(pa + li * G::PL * G::ROWB);
@@ -435,7 +406,7 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
 #endif
         half(0, brick, kh, kw, 1, wslot, 1);
         STAMP(st_h1);
-        block_sync();                                          // the stage's barrier (see the header)
+        lds_barrier();                                         // the stage's barrier (see the header)
         STAMP(st_bar);
         if (t9 < 8) half(1, brick, (t9 + 1) / 3, (t9 + 1) % 3, 0, wslot_nx, 0);
         else half(1, brick_nx, 0, 0, 0, wslot_nx, 0);
@@ -611,7 +582,7 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
           red[(hhalf * 2 + 1) * G::NT + wn * (32 * NTW) + j * 32 + r] = q2;
         }
       }
-      block_sync();
+      lds_barrier();
       if (tid < 2 * G::NT) {
         const int which = tid / G::NT, c = tid % G::NT;
         float t_ = red[(0 * 2 + which) * G::NT + c];
@@ -623,7 +594,7 @@ conv_fwd_brick_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
     st_wo += __builtin_amdgcn_s_memtime() - st_wo0;
 #endif
     if (!has_next) break;
-    block_sync();                       // the loaders may now fetch into the staging slot (their barrier in a brick's first stage)
+    lds_barrier();                      // the loaders may now fetch into the staging slot (their barrier in a brick's first stage)
     tile = tile_nx;
     cur = nxt;
   }

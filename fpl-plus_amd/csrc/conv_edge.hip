@@ -4,25 +4,12 @@
 // They still run on the matrix cores (padding K / N to the 32x32x16 tile) because the VALU
 // formulation is ~10x over the HBM time; with MFMA all five kernels sit at the memory roof.
 #include "internal.h"
+#include "gfx950.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
 constexpr int TH = 8, TW = 32, SH = TH + 2, SW = TW + 2;
-
-__device__ __forceinline__ bf16x8 tr_frag64(const char* base_lo) {      // [voxel][32 ch] image, 64 B rows
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo + 4 * 64));
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
 
 struct Tile { int n, d, h0, w0; };
 // 32-bit index math (2^31 tiles would be 5e11 voxels): a 64-bit division is a ~100-instruction loop
@@ -199,8 +186,6 @@ stem_fwd_mfma(const float* __restrict__ x, const bf16_t* __restrict__ wf, const 
 //   * a lane ends up with 16 output channels of ONE voxel; two v_permlane32_swap exchanges between the lane halves turn
 //     them into two runs of 8 consecutive channels = two 16-byte stores per lane, whole 64-byte voxel rows per wave;
 //   * BatchNorm statistics: 16 + 16 running sums per lane, reduced once at the end of the kernel.
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2e;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4e;
 
 // CIN = 4 (round 4, config 5): the same two MFMAs per input channel - the planar input makes a channel just another base
 // offset, the tap -> k-slot map and the padding selects are shared - 64 loads in flight per lane, two blocks per CU.
@@ -358,14 +343,14 @@ stem_fwd_rows(const float* __restrict__ x, const bf16_t* __restrict__ wf, const 
     for (int g2 = 0; g2 < 2; ++g2)                    // (q0, q1) and (q2, q3): high half of the first <-> low half of the second
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const u32x2e sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
+        const u32x2 sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
         pk[4 * g2 + e] = sw[0];
         pk[4 * g2 + 2 + e] = sw[1];
       }
     if (wc) {
       bf16_t* dst = y + ((int64_t)(((n * D + d) * H + h)) * W + wv) * ldy + co0 + 8 * khalf;
-      *reinterpret_cast<u32x4e*>(dst) = u32x4e{pk[0], pk[1], pk[2], pk[3]};
-      *reinterpret_cast<u32x4e*>(dst + 16) = u32x4e{pk[4], pk[5], pk[6], pk[7]};
+      *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+      *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
     }
   };
   // (The loads of segment t + 1 issued before segment t is computed - 128 registers, still four waves per SIMD - were measured
@@ -480,7 +465,7 @@ stem_wgrad_mfma(const float* __restrict__ x, const bf16_t* __restrict__ dy, int6
     for (int kk = 0; kk < 4; ++kk) {                   // each wave takes 4 of the 16 k-steps (K split)
       const int ks = wave * 4 + kk;
       const int hr = ks >> 1, ws = (ks & 1) * 16;
-      const bf16x8 bfrag = tr_frag64(dys + (hr * TW + ws) * 64 + lane_off);
+      const bf16x8 bfrag = tr_frag(dys + (hr * TW + ws) * 64 + lane_off);
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         bf16x8 a;
@@ -651,7 +636,6 @@ outconv_fwd_mfma(const bf16_t* __restrict__ x, int64_t ldx, const float* __restr
 // tap spans all 32 channels), the weights are the A operand and live in registers for the whole kernel (9 fragments), the only
 // LDS traffic of a tile is one 16-byte read per (tap, 16 voxels), and the result comes out voxel-contiguous: lanes 0-15 hold
 // class 0 / 1 (registers 0 / 1) of 16 consecutive voxels = 64-byte stores into the planar logits.
-typedef __attribute__((ext_vector_type(4))) float f32x4e;
 // BN (round 4, Cin = 32): the input is the PRE-BatchNorm output y of the network's last 3x3x3 convolution; the BatchNorm
 // apply + PReLU pass of that site (fplx_bn_act_fwd, dropout-free) happens HERE, on the staged registers on their way into LDS,
 // and the activation a = PReLU(scale y + shift) - the tensor backward needs - is written out for the tile's own voxels: the
@@ -684,7 +668,7 @@ outconv_fwd_t(const bf16_t* __restrict__ x, int64_t ldx, const float* __restrict
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         afr[tap][s_][j] = r16 < ncls ? (bf16_t)wf[((int64_t)tap * ncls + r16) * CIN + s_ * 32 + 8 * kg + j] : (bf16_t)0.f;
-  f32x4e cinit;                                       // D rows 4 kg + i = classes
+  f32x4 cinit;                                       // D rows 4 kg + i = classes
 #pragma unroll
   for (int i = 0; i < 4; ++i) cinit[i] = (bias && 4 * kg + i < ncls) ? bias[4 * kg + i] : 0.f;
   // 16-byte chunk c of voxel v sits at slot c ^ swz(v) of the voxel's row.  ds_read_b128 is serviced in four groups of 16 lanes
@@ -744,7 +728,7 @@ outconv_fwd_t(const bf16_t* __restrict__ x, int64_t ldx, const float* __restrict
       fetch(tn);
     }
     // a wave owns rows 2 wave, 2 wave + 1 of the tile: four segments of 16 voxels
-    f32x4e acc[4];
+    f32x4 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = cinit;
 #pragma unroll
@@ -815,7 +799,7 @@ outconv_fwd_rows(const bf16_t* __restrict__ y, int64_t ldy, const float* __restr
     }
   }
   __syncthreads();
-  f32x4e cinit;                                       // D rows 4 kg + i = classes
+  f32x4 cinit;                                       // D rows 4 kg + i = classes
 #pragma unroll
   for (int i = 0; i < 4; ++i) cinit[i] = (bias && 4 * kg + i < ncls) ? bias[4 * kg + i] : 0.f;
   float bsc[8], bsh[8];                                // the lane's channel chunk is lane & 3 for all three of its pieces
@@ -852,24 +836,24 @@ outconv_fwd_rows(const bf16_t* __restrict__ y, int64_t ldy, const float* __restr
     const int hA = hs * S, hB = hA + S < H ? hA + S : H;          // the strip's output rows [hA, hB)
     const int64_t plane = ((int64_t)n * D + d) * H;                // voxel index of (n, d, 0, 0) / W
     // ---- loads of input row hh (hA - 1 .. hB): three 16-byte pieces per lane, zeros outside the volume
-    auto issue = [&](int hh, u32x4e (&v)[3]) {
+    auto issue = [&](int hh, u32x4 (&v)[3]) {
       const bool rowin = hh >= 0 && hh < H;
 #pragma unroll
       for (int t_ = 0; t_ < 3; ++t_) {
         const int wv = w0 - 1 + pvox[t_];
         const bool ok = rowin && wv >= 0 && wv < W && (t_ < 2 || p2);
-        v[t_] = ok ? *reinterpret_cast<const u32x4e*>(y + ((plane + hh) * W + wv) * ldy + (lane & 3) * 8) : u32x4e{0u, 0u, 0u, 0u};
+        v[t_] = ok ? *reinterpret_cast<const u32x4*>(y + ((plane + hh) * W + wv) * ldy + (lane & 3) * 8) : u32x4{0u, 0u, 0u, 0u};
       }
     };
     // ---- BatchNorm apply + PReLU on a loaded row, activation out for the strip's own voxels, commit to ring slot (hh + 1) mod 3
-    auto commit = [&](int hh, const u32x4e (&v)[3]) {
+    auto commit = [&](int hh, const u32x4 (&v)[3]) {
       const bool rowin = hh >= 0 && hh < H, rowown = hh >= hA && hh < hB;
       char* slot = ring + ((hh + 1) % 3) * SLOT;       // hh >= -1
 #pragma unroll
       for (int t_ = 0; t_ < 3; ++t_) {
         if (t_ == 2 && !p2) continue;
         const int wv = w0 - 1 + pvox[t_];
-        u32x4e o = u32x4e{0u, 0u, 0u, 0u};
+        u32x4 o = u32x4{0u, 0u, 0u, 0u};
         if (rowin && wv >= 0 && wv < W) {
           bf16x8 v8 = __builtin_bit_cast(bf16x8, v[t_]);
 #pragma unroll
@@ -878,14 +862,14 @@ outconv_fwd_rows(const bf16_t* __restrict__ y, int64_t ldy, const float* __restr
             z = z > 0.f ? z : z * bslope;
             v8[j] = (bf16_t)z;
           }
-          o = __builtin_bit_cast(u32x4e, v8);
+          o = __builtin_bit_cast(u32x4, v8);
           if (aout && rowown && pvox[t_] >= 1 && pvox[t_] <= 32)  // the strip's own voxel: its activation goes to memory (if wanted)
-            *reinterpret_cast<u32x4e*>(aout + ((plane + hh) * W + wv) * lda + (lane & 3) * 8) = o;
+            *reinterpret_cast<u32x4*>(aout + ((plane + hh) * W + wv) * lda + (lane & 3) * 8) = o;
         }
-        *reinterpret_cast<u32x4e*>(slot + poff[t_]) = o;
+        *reinterpret_cast<u32x4*>(slot + poff[t_]) = o;
       }
     };
-    u32x4e ra[3], rb[3], rc[3];
+    u32x4 ra[3], rb[3], rc[3];
     issue(hA - 1, ra);
     issue(hA, rb);
     commit(hA - 1, ra);
@@ -899,7 +883,7 @@ outconv_fwd_rows(const bf16_t* __restrict__ y, int64_t ldy, const float* __restr
       commit(ho + 1, ra);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      f32x4e acc[2] = {cinit, cinit};
+      f32x4 acc[2] = {cinit, cinit};
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh) {
         const char* slot = ring + ((ho + kh) % 3) * SLOT;          // input row ho - 1 + kh sits in slot (ho + kh) mod 3
@@ -1299,7 +1283,7 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
   };
   // one segment's loads: the lane's dlogits (2 classes x 2 taps per k-step) and y of the segment's 32 voxels.  They are issued a
   // whole segment ahead of their use: with three waves per SIMD that keeps about 50 KB of y in flight per CU
-  auto issue = [&](const Seg& g, float (&gv)[KS][4], u32x4e (&yq)[2]) {
+  auto issue = [&](const Seg& g, float (&gv)[KS][4], u32x4 (&yq)[2]) {
     if (g.cn >= (unsigned)N) return;
     const int n = (int)g.cn, d = (int)g.cd, h = (int)g.ch, w0 = (int)g.cw * 32;
     const int sbase = (((n * NCLS * D + d) * H + h) * W + w0) * 4;                     // scalar byte offset in the class-0 plane
@@ -1313,10 +1297,10 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const bool ok = w0 + rv + 16 * q < W;
-      yq[q] = ok ? *reinterpret_cast<const u32x4e*>(yv + (vrow + rv + 16 * q) * ldy + 8 * rrun) : u32x4e{0u, 0u, 0u, 0u};
+      yq[q] = ok ? *reinterpret_cast<const u32x4*>(yv + (vrow + rv + 16 * q) * ldy + 8 * rrun) : u32x4{0u, 0u, 0u, 0u};
     }
   };
-  auto consume = [&](const Seg& g, const float (&gv)[KS][4], const u32x4e (&yq)[2]) {
+  auto consume = [&](const Seg& g, const float (&gv)[KS][4], const u32x4 (&yq)[2]) {
     if (g.cn >= (unsigned)N) return;
     const int n = (int)g.cn, d = (int)g.cd, h = (int)g.ch, w0 = (int)g.cw * 32;
     // ---- out_conv's data gradient of the lane's voxel: 16 channels.  Padding: bit t of `tapok` = tap t lies inside the plane
@@ -1349,7 +1333,7 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
     unsigned pk[8];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const u32x2e sw = __builtin_amdgcn_permlane16_swap(yq[0][e], yq[1][e], false, false);
+      const u32x2 sw = __builtin_amdgcn_permlane16_swap(yq[0][e], yq[1][e], false, false);
       pk[e] = sw[0];
       pk[4 + e] = sw[1];
     }
@@ -1357,7 +1341,7 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
     for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const u32x2e sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
+        const u32x2 sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
         pk[4 * g2 + e] = sw[0];
         pk[4 * g2 + 2 + e] = sw[1];
       }
@@ -1366,10 +1350,10 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
     unsigned ok8[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const f32x4e c0 = *reinterpret_cast<const f32x4e*>(&cst[0][8 * q + 4 * khalf]);
-      const f32x4e c1 = *reinterpret_cast<const f32x4e*>(&cst[1][8 * q + 4 * khalf]);
-      const f32x4e c2 = *reinterpret_cast<const f32x4e*>(&cst[2][8 * q + 4 * khalf]);
-      const f32x4e c3 = *reinterpret_cast<const f32x4e*>(&cst[3][8 * q + 4 * khalf]);
+      const f32x4 c0 = *reinterpret_cast<const f32x4*>(&cst[0][8 * q + 4 * khalf]);
+      const f32x4 c1 = *reinterpret_cast<const f32x4*>(&cst[1][8 * q + 4 * khalf]);
+      const f32x4 c2 = *reinterpret_cast<const f32x4*>(&cst[2][8 * q + 4 * khalf]);
+      const f32x4 c3 = *reinterpret_cast<const f32x4*>(&cst[3][8 * q + 4 * khalf]);
       float o[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1399,19 +1383,19 @@ outconv_dgrad_rows(const float* __restrict__ dl, const bf16_t* __restrict__ wb, 
       for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const u32x2e sw = __builtin_amdgcn_permlane32_swap(ok8[4 * g2 + e], ok8[4 * g2 + 2 + e], false, false);
+          const u32x2 sw = __builtin_amdgcn_permlane32_swap(ok8[4 * g2 + e], ok8[4 * g2 + 2 + e], false, false);
           ok8[4 * g2 + e] = sw[0];
           ok8[4 * g2 + 2 + e] = sw[1];
         }
       if (wc) {
         bf16_t* dst = dx + ((((int64_t)n * D + d) * H + h) * W + wv) * ldx + 8 * khalf;
-        *reinterpret_cast<u32x4e*>(dst) = u32x4e{ok8[0], ok8[1], ok8[2], ok8[3]};
-        *reinterpret_cast<u32x4e*>(dst + 16) = u32x4e{ok8[4], ok8[5], ok8[6], ok8[7]};
+        *reinterpret_cast<u32x4*>(dst) = u32x4{ok8[0], ok8[1], ok8[2], ok8[3]};
+        *reinterpret_cast<u32x4*>(dst + 16) = u32x4{ok8[4], ok8[5], ok8[6], ok8[7]};
       }
     }
   };
   float gA[KS][4], gB[KS][4];
-  u32x4e yA[2], yB[2];
+  u32x4 yA[2], yB[2];
   Seg cur = nx;
   issue(cur, gA, yA);
   for (int64_t tt = tr.first; tt < tr.end; tt += tr.step) {
@@ -1553,7 +1537,7 @@ outconv_wgrad_mfma(const bf16_t* __restrict__ x, int64_t ldx, const float* __res
         const int tap = wave + 4 * a;                  // wave-uniform
         if (tap < 9) {
           const int kh = tap / 3, kw = tap % 3;
-          fa[a] = tr_frag64(xs + ((hr + kh) * SW + ws + kw) * 64 + lane_off);
+          fa[a] = tr_frag(xs + ((hr + kh) * SW + ws + kw) * 64 + lane_off);
         }
       }
     };
@@ -1640,7 +1624,7 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
   for (int j = 0; j < 8; ++j) { bsc[j] = bn_scale[chunk * 8 + j]; bsh[j] = bn_shift[chunk * 8 + j]; }
   const float bslope = *slope_p;
   const int g4 = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
-  const int lane_off = (8 * (g4 >> 1) + q4) * 64 + (16 * (g4 & 1) + 4 * p4) * 2;      // tr_frag64: row = channel lane & 31
+  const int lane_off = (8 * (g4 >> 1) + q4) * 64 + (16 * (g4 & 1) + 4 * p4) * 2;      // tr_frag: row = channel lane & 31
   // ---- B side: the lane's pair
   const bool pok = r < npair;
   const int tap = pok ? r / ncls : 4, cls = pok ? r % ncls : 0;
@@ -1682,7 +1666,7 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
     g.cd -= carry ? uD : 0u;
     g.cn += sn_ + carry;
   };
-  auto issue = [&](const Seg& g, u32x4e (&gq)[4], u32x4e (&yq)[2]) {
+  auto issue = [&](const Seg& g, u32x4 (&gq)[4], u32x4 (&yq)[2]) {
     if (g.cn >= (unsigned)N) return;
     const int n = (int)g.cn, d = (int)g.cd, h = (int)g.ch, w0 = (int)g.cw * 32;
     const int sbase = (((n * ncls * D + d) * H + h) * W + w0) * 4;         // byte offset of the segment in the class-0 plane
@@ -1696,31 +1680,31 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
         const int ok = o + (k >> 1) * 64 + (k & 1) * 16;
         const bool neg = ok < 0;
         int ol = neg ? 0 : ok;
-        asm volatile("" : "+v"(ol));                     // (one opaque offset: no base + immediate split of a negative base)
-        const u32x4e q = __builtin_bit_cast(u32x4e, __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowok ? (unsigned)ol : 0x80000000u, 0, 0));
-        gq[k] = neg ? u32x4e{0u, q.x, q.y, q.z} : q;
+        opaque_v(ol);                                    // (one opaque offset: no base + immediate split of a negative base)
+        const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowok ? (unsigned)ol : 0x80000000u, 0, 0));
+        gq[k] = neg ? u32x4{0u, q.x, q.y, q.z} : q;
       }
     } else {
       const unsigned vo = rowok ? (unsigned)o : 0x80000000u;
       // (a window that reaches beyond the tensor's last byte returns zeros there: raw buffers are range-checked per dword)
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        gq[k] = __builtin_bit_cast(u32x4e, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo + (unsigned)((k >> 1) * 64 + (k & 1) * 16), 0, 0));
+        gq[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo + (unsigned)((k >> 1) * 64 + (k & 1) * 16), 0, 0));
     }
     const int64_t vrow = (((int64_t)n * D + d) * H + h) * W + w0;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const bool ok = w0 + pv + 16 * t < W;
-      yq[t] = ok ? *reinterpret_cast<const u32x4e*>(yv + (vrow + pv + 16 * t) * ldy + 8 * chunk) : u32x4e{0u, 0u, 0u, 0u};
+      yq[t] = ok ? *reinterpret_cast<const u32x4*>(yv + (vrow + pv + 16 * t) * ldy + 8 * chunk) : u32x4{0u, 0u, 0u, 0u};
     }
   };
-  auto consume = [&](const Seg& g, const u32x4e (&gq)[4], const u32x4e (&yq)[2]) {
+  auto consume = [&](const Seg& g, const u32x4 (&gq)[4], const u32x4 (&yq)[2]) {
     if (g.cn >= (unsigned)N) return;
     const int w0 = (int)g.cw * 32;
     // ---- a = PReLU(scale y + shift) -> bf16 into the tile (zeros beyond W: such voxels then add nothing to any sum)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      u32x4e o = u32x4e{0u, 0u, 0u, 0u};
+      u32x4 o = u32x4{0u, 0u, 0u, 0u};
       if (w0 + pv + 16 * t < W) {
         bf16x8 v8 = __builtin_bit_cast(bf16x8, yq[t]);
 #pragma unroll
@@ -1729,16 +1713,16 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
           z = z > 0.f ? z : z * bslope;
           v8[j] = (bf16_t)z;
         }
-        o = __builtin_bit_cast(u32x4e, v8);
+        o = __builtin_bit_cast(u32x4, v8);
       }
-      *reinterpret_cast<u32x4e*>(atile + (lane + 64 * t) * 16) = o;
+      *reinterpret_cast<u32x4*>(atile + (lane + 64 * t) * 16) = o;
     }
     // ---- g: columns outside the plane are zeros (only the segments that touch a row end have any)
     float gf[16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       // (whole-vector cast: __builtin_bit_cast(float, gq[k][e]) on a vector ELEMENT reads element 0 with this compiler)
-      const f32x4e q = __builtin_bit_cast(f32x4e, gq[k]);
+      const f32x4 q = __builtin_bit_cast(f32x4, gq[k]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) gf[4 * k + e] = q[e];
     }
@@ -1756,7 +1740,7 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const bf16x8 fa = tr_frag64(atile + 16 * s * 64 + lane_off);
+      const bf16x8 fa = tr_frag(atile + 16 * s * 64 + lane_off);
       bf16x8 fb;
 #pragma unroll
       for (int j = 0; j < 8; ++j) fb[j] = (bf16_t)gf[8 * s + j];
@@ -1764,7 +1748,7 @@ outconv_wgrad_rows(const bf16_t* __restrict__ yv, int64_t ldy, const float* __re
     }
     __builtin_amdgcn_wave_barrier();                   // the tile is rewritten by the next segment
   };
-  u32x4e gA[4], gB[4], yA[2], yB[2];
+  u32x4 gA[4], gB[4], yA[2], yB[2];
   Seg cur = nx;
   issue(cur, gA, yA);
   for (int64_t tt = tr.first; tt < tr.end; tt += tr.step) {

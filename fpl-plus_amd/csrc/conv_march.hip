@@ -20,6 +20,7 @@
 // reference PyMIC/pymic/net/net3d/unet2d5_dsbn.py:54-55,75,79 (ConvolutionLayer / ConvBlockND), and the
 // torch.cat of unet2d5_dsbn.py:182 when the input / output is given as two tensors (x1 / y1).
 #include "internal.h"
+#include "gfx950.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -29,18 +30,6 @@ __device__ __attribute__((aligned(16))) const unsigned int fplx_zero16[4] = {0u,
 #ifdef FPLX_STAMP
 __device__ long long* fplx_stamp_buf;      // set by the micro-benchmark
 #endif
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-// Barrier for LDS traffic only.  __syncthreads() also waits for vmcnt(0), i.e. for the acknowledgement of every global store
-// the wave has in flight - at the end of a block that is the whole write-out of its last depth (2-3 us per block, 12-24 us
-// per launch measured on the statistics forms); the statistics tail only exchanges LDS data.  Callers guarantee that no
-// LDS-DMA is in flight (the march loops end with vmcnt(0) + barrier).
-#define FPLX_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 struct MG {
   static constexpr int CIN = 32, ROWB = 64, CH = 4;
@@ -68,7 +57,7 @@ __device__ __forceinline__ void march_step(const char* __restrict__ sl, const ch
   // computed next to their use (a handful of VALU ops under the MFMAs) instead of being hoisted out of the depth
   // loop and spilled
   int vb = wave * 2 * MG::SW + r, rb = r;
-  asm volatile("" : "+v"(vb), "+v"(rb));
+  opaque_v(vb, rb);
   // weight rows: swz(tap * 32 + r) == swz(r), so a tap is an immediate offset from two lane bases
   const char* wl0 = wbuf + rb * MG::ROWB + ((khalf ^ MG::swz(rb)) << 4);
   const char* wl1 = wbuf + rb * MG::ROWB + (((2 + khalf) ^ MG::swz(rb)) << 4);
@@ -135,22 +124,10 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   const int d1 = (d0 + dlen < D) ? d0 + dlen : D;
   const int n0 = bid.y * 32;
 
-  // global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write pass).  A wave-instruction
-  // fills 1 KiB = 16 voxel rows linearly, so the XOR swizzle is applied to each lane's SOURCE chunk; halo voxels
-  // outside the volume read a 16-byte zero constant.
-  // Issued as inline asm: with the builtin in the loop hipcc stops counting lgkmcnt and drains every ds_read with
-  // lgkmcnt(0), which defeats the fragment prefetch.  The DMA is retired by the explicit vmcnt(0) in front of the
-  // barrier that publishes the slab.
-  auto lds_dma = [&](const void* g, char* l) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)l));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-  };
-  // vmcnt(0) retires this wave's DMA pieces (and its output stores: loads and stores share the counter and may
-  // complete out of order, so only 0 is a safe count); the raw barrier then publishes the slab to the block
-  auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  // global -> LDS by LDS-DMA (lds_dma_global, gfx950.h).  A wave-instruction fills 1 KiB = 16 voxel rows linearly, so the
+  // XOR swizzle is applied to each lane's SOURCE chunk; halo voxels outside the volume read a 16-byte zero constant.
+  // wait_vmcnt0() retires this wave's DMA pieces (and its output stores: loads and stores share the counter and may
+  // complete out of order, so only 0 is a safe count); lds_barrier() then publishes the slab to the block
   constexpr int NPIECE = MG::NPIECE;
   // per lane and piece: byte offset of the source chunk inside one depth slice of x, or -1 for the zero constant
   // (halo outside the volume, and the tail of the last 1-KiB piece).  Parked in LDS: as registers they would be
@@ -170,7 +147,7 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
     if (wave + 8 * k < MG::SLAB_DMA) {
       const char* xs = xn + s * xslice;                   // uniform
       const void* src = so >= 0 ? (const void*)(xs + (unsigned)so) : (const void*)fplx_zero16;
-      lds_dma(src, slabs + ((s + 1) & 1) * MG::SLAB_BYTES + (wave + 8 * k) * 1024);
+      lds_dma_global(src, lds_addr(slabs + ((s + 1) & 1) * MG::SLAB_BYTES + (wave + 8 * k) * 1024));
     }
   };
 
@@ -191,11 +168,11 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   for (int j = wave; j < 27 * 32 * MG::CH / 64; j += 8) {
     const int i = j * 64 + lane;
     const int row = i >> 2, c = (i & 3) ^ MG::swz(row);
-    lds_dma(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * MG::CIN + c * 8, wbuf + j * 1024);
+    lds_dma_global(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * MG::CIN + c * 8, lds_addr(wbuf + j * 1024));
   }
   if (tid < 32) bias_s[tid] = bias ? bias[n0 + tid] : 0.f;
-  dma_wait();
-  block_sync();
+  wait_vmcnt0();
+  lds_barrier();
 
   // write-out of a finished depth o: lane = output channel r, registers = 16 voxels of the M-tile's w-row.
   // retire_pair handles voxels i0, i0 + 1 of both M-tiles (called from 8 stages), retire_zero clears the set.
@@ -236,19 +213,13 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   auto retire_flush = [&](int m, int o) {                 // LDS tile -> y, two 16-byte stores per lane
     if (m ? hok1 : hok0) {
       unsigned l2 = ldy2;
-      asm volatile("" : "+s"(l2));
+      opaque_s(l2);
       char* rowp = yn + o * yslice + (unsigned)(m * W) * l2;            // uniform
       const u32x4 v0 = *reinterpret_cast<const u32x4*>(stg_r);
       const u32x4 v1 = *reinterpret_cast<const u32x4*>(stg_r + 1024);
-      // inline asm: a store hipcc knows about makes it guard later register reuse with vmcnt(N) waits, and since it
-      // does not know about the DMA pieces in flight, those waits end up waiting for the DMA.
-      // s_nop 1: a VMEM store of more than 8 bytes reads its data VGPRs for two more cycles ("12-dword store" hazard:
-      // a VALU write of those registers needs 2 wait states on gfx940+); hipcc's hazard recognizer does not look inside
-      // inline asm, and the register allocator reuses v0 / v1 at once.  Without the nop the first dword of the store's
-      // last lanes picked up the next instruction's result whenever another kernel's waves shared the SIMD
-      // (profiles/r02_race25_hazard_location.txt: the 2.5D stream-order hazard of round 1)
-      if (sok0) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(v0) : "memory");
-      if (sok1) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + 16u * l2 + soffb), "v"(v1) : "memory");
+      // stores hipcc does not see, with their own wait states: see global_store_16 (gfx950.h)
+      if (sok0) global_store_16(rowp + soffb, v0);
+      if (sok1) global_store_16(rowp + 16u * l2 + soffb, v1);
     }
   };
 
@@ -317,11 +288,11 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
 #ifdef FPLX_STAMP
     const long long st1 = __builtin_amdgcn_s_memtime();
 #endif
-    dma_wait();                                        // slab s + 1 landed and the stores left stages ago
+    wait_vmcnt0();                                      // slab s + 1 landed and the stores left stages ago
 #ifdef FPLX_STAMP
     const long long st2 = __builtin_amdgcn_s_memtime();
 #endif
-    block_sync();
+    lds_barrier();
 #ifdef FPLX_STAMP
     const long long st3 = __builtin_amdgcn_s_memtime();
     st_step += st1 - st0; st_wait += st2 - st1; st_bar += st3 - st2;
@@ -345,11 +316,11 @@ conv_fwd_march32(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   }
 
   if (stats) {
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     float* red = reinterpret_cast<float*>(smem);            // [8 waves][2][32]; the slabs are dead
     const float a = ssum + __shfl_xor(ssum, 32, 64), q2 = qsum + __shfl_xor(qsum, 32, 64);
     if (lane < 32) { red[(wave * 2 + 0) * 32 + r] = a; red[(wave * 2 + 1) * 32 + r] = q2; }
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     if (tid < 64) {
       const int which = tid >> 5, c = tid & 31;
       float t = 0.f;
@@ -412,14 +383,6 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   const int d1 = (d0 + dlen < D) ? d0 + dlen : D;
   const int n0 = bid.y * 32;
 
-  auto lds_dma = [&](const void* g, char* l) {          // see conv_fwd_march32 (the resident weights come this way)
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)l));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-  };
-  auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   constexpr int NPIECE = G::NPIECE;
   // Slab DMA through a buffer descriptor over this sample's volume (base x[n], num_records = D slices): `buffer_load_dwordx4
   // ... offen lds` with a per-lane byte offset inside the depth slice (a constant of the whole march), the depth as the
@@ -442,6 +405,7 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   }
   const int64_t xslice = (int64_t)H * W * ldx * 2;
   const char* xn = reinterpret_cast<const char*>(x) + (int64_t)n * D * xslice;
+  // (written out, not buffer_rsrc(): through the constructor hipcc orders this kernel's fragment registers differently)
   u32x4 rsrc;
   rsrc[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
   rsrc[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
@@ -451,12 +415,9 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto slab_piece = [&](int s, int k, unsigned vo) {    // piece k of slab s -> slot (s + 1) & 1; vo = voff_s[k][tid]
     int piece = wave + G::WAVES * k;
     if (piece > G::SLAB_DMA - 1) piece = G::SLAB_DMA - 1;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(size_t)((__attribute__((address_space(3))) char*)(slabs + ((s + 1) & 1) * G::SLAB_BYTES + piece * 1024)));
+    const unsigned dst = lds_addr(slabs + ((s + 1) & 1) * G::SLAB_BYTES + piece * 1024);
     const unsigned so = __builtin_amdgcn_readfirstlane((s >= 0 && s < D) ? (unsigned)s * xslice32 : 0x40000000u);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so), "s"(dst) : "memory");
+    lds_dma_buffer(rsrc, vo, so, dst);
   };
 
   // accumulator sets: at step t role j (K0 = depth s + 1, K1 = s, K2 = s - 1, R = being written out) is set (j - t) & 3
@@ -475,11 +436,11 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   for (int j = wave; j < 27 * 32 * G::CH / 64; j += G::WAVES) {
     const int i = j * 64 + lane;
     const int row = i >> 2, c = (i & 3) ^ G::swz(row);
-    lds_dma(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * G::CIN + c * 8, wbuf + j * 1024);
+    lds_dma_global(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * G::CIN + c * 8, lds_addr(wbuf + j * 1024));
   }
   if (tid < 32) bias_s[tid] = bias ? bias[n0 + tid] : 0.f;
-  dma_wait();
-  block_sync();
+  wait_vmcnt0();
+  lds_barrier();
 
   const float bv = bias_s[r];
   float ssum = 0.f, qsum = 0.f;
@@ -503,12 +464,12 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto retire_flush = [&](int m, int o) {
     const char* r_ = stg + (m & 1) * G::STAGE_BYTES + lane * 16;
     unsigned l2 = ldy2;
-    asm volatile("" : "+s"(l2));
+    opaque_s(l2);
     char* rowp = yn + o * yslice + (unsigned)(m * W) * l2;
     const u32x4 v0 = *reinterpret_cast<const u32x4*>(r_);
     const u32x4 v1 = *reinterpret_cast<const u32x4*>(r_ + 1024);
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(v0) : "memory");
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + 16u * l2 + soffb), "v"(v1) : "memory");
+    global_store_16(rowp + soffb, v0);
+    global_store_16(rowp + 16u * l2 + soffb, v1);
   };
 
   const int nd = d1 - d0;                         // >= 2 (march_cfg)
@@ -533,7 +494,7 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto load_a = [&](const char* sl, int g, int buf) {    // g = kw * 2 + ks
     const int kw = g >> 1, ks = g & 1, c = 2 * ks + khalf;
     int vb = wave * 4 * G::SW + r;
-    asm volatile("" : "+v"(vb));                         // lane bases re-derived at the point of use (no hoisted address zoo)
+    opaque_v(vb);                         // lane bases re-derived at the point of use (no hoisted address zoo)
 #pragma unroll
     for (int rho = 0; rho < 6; ++rho) {
       const int vox = vb + rho * G::SW + kw;
@@ -543,7 +504,7 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto load_b = [&](int g, int kd) {
     const int kw = g >> 1, ks = g & 1;
     int rb = r;
-    asm volatile("" : "+v"(rb));
+    opaque_v(rb);
     const char* wl = wbuf + rb * G::ROWB + (((2 * ks + khalf) ^ G::swz(rb)) << 4);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
@@ -593,10 +554,10 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
       load_b((g + 1) % 6, 0);
       if (g >= 1 && g <= 4) {
         unsigned l2 = ldy2;
-        asm volatile("" : "+s"(l2));
+        opaque_s(l2);
         char* rowp = yn + o * yslice + (unsigned)((g - 1) * W) * l2;
-        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(fl0) : "memory");
-        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + 16u * l2 + soffb), "v"(fl1) : "memory");
+        global_store_16(rowp + soffb, fl0);
+        global_store_16(rowp + 16u * l2 + soffb, fl1);
       }
       if (np > 0) {
         slab_piece(s + 1, p0, vo0);
@@ -624,8 +585,8 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
       load_b((g + 1) % 6, 2);
       __builtin_amdgcn_sched_barrier(0);
       if (g == 4) {                                      // the next slab has landed; nobody reads this one any more
-        dma_wait();
-        block_sync();
+        wait_vmcnt0();
+        lds_barrier();
       }
     }
   };
@@ -671,11 +632,11 @@ conv_fwd_march32v2(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   }
 
   if (STATS && stats) {
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     float* red = reinterpret_cast<float*>(smem);            // [4 waves][2][32]; the slabs are dead
     const float a = ssum + __shfl_xor(ssum, 32, 64), q2 = qsum + __shfl_xor(qsum, 32, 64);
     if (lane < 32) { red[(wave * 2 + 0) * 32 + r] = a; red[(wave * 2 + 1) * 32 + r] = q2; }
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     if (tid < 64) {
       const int which = tid >> 5, c = tid & 31;
       float tt = 0.f;
@@ -727,14 +688,6 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   // XORed by 2 * ((vox >> 2) & 1); the (vox >> 2) & 3 of the 32 x 32 x 16 kernels costs this read pattern 2-way conflicts in
   // most lane groups (SQ_LDS_BANK_CONFLICT 0.31 of the LDS cycles, profiles/r02_pmc_sq_counters.txt)
   auto aswz = [](int vox) { return ASWZ ? ((vox >> 2) & 1) << 1 : (vox >> 2) & 3; };
-  auto lds_dma = [&](const void* g, char* l) {          // see conv_fwd_march32 (the resident weights come this way)
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)l));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-  };
-  auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   constexpr int NPIECE = G::NPIECE;
   // Slab DMA through a buffer descriptor over this sample's volume (base x[n], num_records = D slices): `buffer_load_dwordx4
   // ... offen lds` with a per-lane byte offset inside the depth slice (a constant of the whole march), the depth as the
@@ -757,6 +710,7 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   }
   const int64_t xslice = (int64_t)H * W * ldx * 2;
   const char* xn = reinterpret_cast<const char*>(x) + (int64_t)n * D * xslice;
+  // (written out, not buffer_rsrc(): through the constructor hipcc orders this kernel's fragment registers differently)
   u32x4 rsrc;
   rsrc[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
   rsrc[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
@@ -766,12 +720,9 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto slab_piece = [&](int s, int k, unsigned vo) {    // piece k of slab s -> slot (s + 1) & 1; vo = voff_s[k][tid]
     int piece = wave + G::WAVES * k;
     if (piece > G::SLAB_DMA - 1) piece = G::SLAB_DMA - 1;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(
-        (unsigned)(size_t)((__attribute__((address_space(3))) char*)(slabs + ((s + 1) & 1) * G::SLAB_BYTES + piece * 1024)));
+    const unsigned dst = lds_addr(slabs + ((s + 1) & 1) * G::SLAB_BYTES + piece * 1024);
     const unsigned so = __builtin_amdgcn_readfirstlane((s >= 0 && s < D) ? (unsigned)s * xslice32 : 0x40000000u);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so), "s"(dst) : "memory");
+    lds_dma_buffer(rsrc, vo, so, dst);
   };
 
   // accumulator sets: at step t role j (K0 = depth s + 1, K1 = s, K2 = s - 1, R = being written out) is set (j - t) & 3
@@ -792,11 +743,11 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   for (int j = wave; j < 27 * 32 * G::CH / 64; j += G::WAVES) {
     const int i = j * 64 + lane;
     const int row = i >> 2, c = (i & 3) ^ wswz(row);
-    lds_dma(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * G::CIN + c * 8, wbuf + j * 1024);
+    lds_dma_global(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * G::CIN + c * 8, lds_addr(wbuf + j * 1024));
   }
   if (tid < 32) bias_s[tid] = bias ? bias[n0 + tid] : 0.f;
-  dma_wait();
-  block_sync();
+  wait_vmcnt0();
+  lds_barrier();
 
   const float bv0 = bias_s[r16], bv1 = bias_s[16 + r16];
   float ssum0 = 0.f, qsum0 = 0.f, ssum1 = 0.f, qsum1 = 0.f;
@@ -823,12 +774,12 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto retire_flush = [&](int m, int o) {
     const char* r_ = stg + (m & 1) * G::STAGE_BYTES + lane * 16;
     unsigned l2 = ldy2;
-    asm volatile("" : "+s"(l2));
+    opaque_s(l2);
     char* rowp = yn + o * yslice + (unsigned)(m * W) * l2;
     const u32x4 v0 = *reinterpret_cast<const u32x4*>(r_);
     const u32x4 v1 = *reinterpret_cast<const u32x4*>(r_ + 1024);
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(v0) : "memory");
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + 16u * l2 + soffb), "v"(v1) : "memory");
+    global_store_16(rowp + soffb, v0);
+    global_store_16(rowp + 16u * l2 + soffb, v1);
   };
 
   const int nd = d1 - d0;                         // >= 2 (march_cfg)
@@ -856,7 +807,7 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   auto load_a = [&](const char* sl, int g, int buf) {    // g = kw * 2 + mh
     const int kw = g >> 1, mh = g & 1;
     int vb = wave * 4 * G::SW + r16;
-    asm volatile("" : "+v"(vb));
+    opaque_v(vb);
 #pragma unroll
     for (int rho = 0; rho < 6; ++rho) {
       const int vox = vb + rho * G::SW + kw + mh * 16;
@@ -865,7 +816,7 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   };
   auto load_b = [&](int kw, int kd) {                    // the six fragments (kh, cout half) of depth tap kd
     int rb = r16;
-    asm volatile("" : "+v"(rb));
+    opaque_v(rb);
     const char* wl = wbuf + rb * G::ROWB + ((kg ^ wswz(rb)) << 4);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
@@ -920,10 +871,10 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
       if (mh == 1) load_b((kw + 1) % 3, 0);
       if (g >= 1 && g <= 4) {
         unsigned l2 = ldy2;
-        asm volatile("" : "+s"(l2));
+        opaque_s(l2);
         char* rowp = yn + o * yslice + (unsigned)((g - 1) * W) * l2;
-        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(fl0) : "memory");
-        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + 16u * l2 + soffb), "v"(fl1) : "memory");
+        global_store_16(rowp + soffb, fl0);
+        global_store_16(rowp + 16u * l2 + soffb, fl1);
       }
       if (np > 0) {
         slab_piece(s + 1, p0, vo0);
@@ -955,8 +906,8 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
       if (mh == 1) load_b((kw + 1) % 3, 2);
       __builtin_amdgcn_sched_barrier(0);
       if (g == 4) {                                      // the next slab has landed; nobody reads this one any more
-        dma_wait();
-        block_sync();
+        wait_vmcnt0();
+        lds_barrier();
       }
     }
   };
@@ -1002,7 +953,7 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
   }
 
   if (STATS && stats) {
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     float* red = reinterpret_cast<float*>(smem);            // [4 waves][2][32]; the slabs are dead
     float a0 = ssum0, a1 = ssum1, q0 = qsum0, q1 = qsum1;   // lanes l, l ^ 16, l ^ 32, l ^ 48 hold the same two channels
     a0 += __shfl_xor(a0, 16, 64); a0 += __shfl_xor(a0, 32, 64);
@@ -1013,7 +964,7 @@ conv_fwd_march32v3(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __re
       red[(wave * 2 + 0) * 32 + r16] = a0; red[(wave * 2 + 0) * 32 + 16 + r16] = a1;
       red[(wave * 2 + 1) * 32 + r16] = q0; red[(wave * 2 + 1) * 32 + 16 + r16] = q1;
     }
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     if (tid < 64) {
       const int which = tid >> 5, c = tid & 31;
       float tt = 0.f;
@@ -1059,7 +1010,7 @@ __device__ __forceinline__ void march64_half(const char* __restrict__ sl, const 
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // M-tile m of this wave starts at footprint row (2 * wave + m) * HPM; lane row r is voxel (r / FW, r % FW) of it
   int vb = (wave * 2 * G::HPM + r / G::FW) * G::SW + r % G::FW, rb = r;
-  asm volatile("" : "+v"(vb), "+v"(rb));         // lane bases re-derived per half-step (no hoisted address zoo)
+  opaque_v(vb, rb);                             // lane bases re-derived per half-step (no hoisted address zoo)
   const char* wl0 = wh + rb * G::ROWB + ((khalf ^ G::swz(rb)) << 4);
   const char* wl1 = wh + rb * G::ROWB + (((2 + khalf) ^ G::swz(rb)) << 4);
   auto load_a = [&](int q, int m) {
@@ -1130,14 +1081,6 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   const int d1 = (d0 + dlen < D) ? d0 + dlen : D;
   const int n0 = bid.y * 32;
 
-  auto lds_dma = [&](const void* g, const char* l) {         // see conv_fwd_march32
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((const __attribute__((address_space(3))) char*)l));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-  };
-  auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   constexpr int NPIECE = G::NPIECE;
   // per lane and piece: byte offset of the source chunk (channel half 0) inside one depth slice of x, -1 = zero,
   // -2 = lane past the end of the slab (the last piece is 16 lanes wide)
@@ -1160,7 +1103,7 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
     if (wave + 4 * k < G::SLAB_DMA && soff[k] != -2) {
       const char* xs = (NQ == 2 ? (hf ? xn1 : xn) : xn + hf * 64) + s * xslice;        // uniform
       const void* src = soff[k] >= 0 ? (const void*)(xs + (unsigned)soff[k]) : (const void*)fplx_zero16;
-      lds_dma(src, slabs + (hf & 1) * G::SLAB_BYTES + (wave + 4 * k) * 1024);
+      lds_dma_global(src, lds_addr(slabs + (hf & 1) * G::SLAB_BYTES + (wave + 4 * k) * 1024));
     }
   };
   // NQ = 4: 1-KiB piece j (0..53: 16 rows [tap j / 2][co (j & 1) * 16 ..] x 4 chunks) of weight quarter qt -> slot qt & 1
@@ -1169,7 +1112,7 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
                       (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
   auto w_piece = [&](int qt, int j) {
     const int64_t row0 = (int64_t)(j >> 1) * Cout + (j & 1) * 16;      // uniform
-    lds_dma(wlane + row0 * (CIN * 2) + qt * 64, wbuf + (qt & 1) * G::WH_BYTES + j * 1024);
+    lds_dma_global(wlane + row0 * (CIN * 2) + qt * 64, lds_addr(wbuf + (qt & 1) * G::WH_BYTES + j * 1024));
   };
 
   f32x16 K0a, K0b, K1a, K1b, K2a, K2b, Ra, Rb;
@@ -1187,14 +1130,14 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
       const int i = j * 64 + lane;                           // chunk index over [half][tap][co][4 chunks]
       const int hf = i / (27 * 32 * G::CH), ii = i % (27 * 32 * G::CH);
       const int row = ii >> 2, c = (ii & 3) ^ G::swz(row);
-      lds_dma(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * 64 + hf * 32 + c * 8, wbuf + j * 1024);
+      lds_dma_global(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * 64 + hf * 32 + c * 8, lds_addr(wbuf + j * 1024));
     }
   } else {
     for (int j = wave; j < 54; j += 4) w_piece(0, j);
   }
   if (tid < 32) bias_s[tid] = bias ? bias[n0 + tid] : 0.f;
-  dma_wait();
-  block_sync();
+  wait_vmcnt0();
+  lds_barrier();
 
   const float bv = bias_s[r];
   float ssum = 0.f, qsum = 0.f;
@@ -1241,12 +1184,12 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   auto retire_flush = [&](int m, int o) {
     if (sok[m][0] || sok[m][1]) {
       unsigned l2 = ldy2;
-      asm volatile("" : "+s"(l2));
+      opaque_s(l2);
       char* rowp = yn + o * yslice + (unsigned)(m * G::HPM * W) * l2;
       const u32x4 v0 = *reinterpret_cast<const u32x4*>(stg_r);
       const u32x4 v1 = *reinterpret_cast<const u32x4*>(stg_r + 1024);
-      if (sok[m][0]) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(v0) : "memory");
-      if (sok[m][1]) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + step1 * l2 + soffb), "v"(v1) : "memory");
+      if (sok[m][0]) global_store_16(rowp + soffb, v0);
+      if (sok[m][1]) global_store_16(rowp + step1 * l2 + soffb, v1);
     }
   };
 
@@ -1312,8 +1255,8 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
         }
       }
 #undef M64_STEP
-      dma_wait();
-      block_sync();
+      wait_vmcnt0();
+      lds_barrier();
     }
     Ra = K2a; Rb = K2b; K2a = K1a; K2b = K1b; K1a = K0a; K1b = K0b;
   }
@@ -1326,11 +1269,11 @@ conv_fwd_march64(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __rest
   retire_flush(1, d1 - 1);
 
   if (stats) {
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     float* red = reinterpret_cast<float*>(smem);            // [4 waves][2][32]; the slabs are dead
     const float a = ssum + __shfl_xor(ssum, 32, 64), q2 = qsum + __shfl_xor(qsum, 32, 64);
     if (lane < 32) { red[(wave * 2 + 0) * 32 + r] = a; red[(wave * 2 + 1) * 32 + r] = q2; }
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     if (tid < 64) {
       const int which = tid >> 5, c = tid & 31;
       float tt = 0.f;
@@ -1378,13 +1321,6 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
   const int d0 = __builtin_amdgcn_readfirstlane(seg * dlen);
   const int d1 = (d0 + dlen < D) ? d0 + dlen : D;
   const int n0 = bid.y * 32;
-  auto lds_dma = [&](const void* g, const char* l) {
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((const __attribute__((address_space(3))) char*)l));
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(dst) : "memory");
-  };
-  auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   constexpr int CIN = NQ * 32;
   const int sbase = TWOD ? d0 : d0 - 1;
   const int nd = d1 - d0;                         // >= 2 (march_cfg)
@@ -1395,14 +1331,14 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
       const int i = j * 64 + lane;                           // chunk index over [half][tap][co][4 chunks]
       const int hf = i / (27 * 32 * G::CH), ii = i % (27 * 32 * G::CH);
       const int row = ii >> 2, c = (ii & 3) ^ G::swz(row);
-      lds_dma(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * 64 + hf * 32 + c * 8, wbuf + j * 1024);
+      lds_dma_global(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * 64 + hf * 32 + c * 8, lds_addr(wbuf + j * 1024));
     }
   }
   const char* wlane = reinterpret_cast<const char*>(wp) + ((int64_t)(n0 + (lane >> 2)) * CIN) * 2 +
                       (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
   auto w_piece = [&](int qt, int j) {
     const int64_t row0 = (int64_t)(j >> 1) * Cout + (j & 1) * 16;      // uniform
-    lds_dma(wlane + row0 * (CIN * 2) + qt * 64, wbuf + (qt & 1) * G::WH_BYTES + j * 1024);
+    lds_dma_global(wlane + row0 * (CIN * 2) + qt * 64, lds_addr(wbuf + (qt & 1) * G::WH_BYTES + j * 1024));
   };
   if constexpr (NQ != 2) {
     for (int j = wave8; j < 54; j += 8) w_piece(0, j);
@@ -1426,26 +1362,18 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
     const int64_t xslice = (int64_t)H * W * ldx * 2;
     const char* xn = reinterpret_cast<const char*>(x) + (int64_t)(nmod0 > 0 ? n % nmod0 : n) * D * xslice;
     const char* xn1 = reinterpret_cast<const char*>(x1 ? x1 : x + 32) + (int64_t)n * D * xslice;
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
+    const unsigned lds0 = lds_addr(smem);
     auto slab_part = [&](int s_, int hf) {                   // all of this wave's pieces of channel part hf of slab s_ -> slot hf & 1
       const char* xs = (NQ == 2 ? (hf ? xn1 : xn) : xn + hf * 64) + s_ * xslice;        // uniform
-      u32x4 rx;
-      rx[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xs);
-      rx[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xs >> 32) & 0xFFFFu);
-      rx[2] = __builtin_amdgcn_readfirstlane((unsigned)xslice);
-      rx[3] = 0x00020000u;
+      const u32x4 rx = buffer_rsrc(xs, xslice);
 #pragma unroll
       for (int k = 0; k < NPIECE; ++k)
-        if (wave + 4 * k < G::SLAB_DMA && soff[k] != 0xFFFFFFFFu) {
-          const unsigned dst = lds0 + (unsigned)((hf & 1) * G::SLAB_BYTES + (wave + 4 * k) * 1024);
-          unsigned keep;
-          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(soff[k]), "s"(rx), "s"(0u), "s"(dst) : "memory");
-        }
+        if (wave + 4 * k < G::SLAB_DMA && soff[k] != 0xFFFFFFFFu)
+          lds_dma_buffer(rx, soff[k], 0u, lds0 + (unsigned)((hf & 1) * G::SLAB_BYTES + (wave + 4 * k) * 1024));
     };
     if (sbase >= 0) slab_part(sbase, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    block_sync();                                            // P0
+    wait_vmcnt0();
+    lds_barrier();                                           // P0
     for (int t = 0; t < nsteps; ++t) {
       const int s = sbase + t;
       const bool live = TWOD ? t < nd : (s >= 0 && s < D);
@@ -1459,11 +1387,11 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
           if (wfetch)
             for (int j = (TWOD ? 18 : 0) + wave; j < (TWOD ? 36 : 54); j += 4) w_piece(nh, j);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        block_sync();
+        wait_vmcnt0();
+        lds_barrier();
       }
     }
-    if (stats) { block_sync(); block_sync(); }               // the compute waves' statistics tail
+    if (stats) { lds_barrier(); lds_barrier(); }               // the compute waves' statistics tail
     return;
   }
 
@@ -1471,8 +1399,8 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
   f32x16 K0a, K0b, K1a, K1b, K2a, K2b, Ra, Rb;
 #pragma unroll
   for (int i = 0; i < 16; ++i) K0a[i] = K0b[i] = K1a[i] = K1b[i] = K2a[i] = K2b[i] = Ra[i] = Rb[i] = 0.f;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's share of the weights
-  block_sync();                                              // P0
+  wait_vmcnt0();           // this wave's share of the weights
+  lds_barrier();                                             // P0
 
   const float bv = bias_s[r];
   float ssum = 0.f, qsum = 0.f;
@@ -1515,12 +1443,12 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
   auto retire_flush = [&](int m, int o) {
     if (sok[m][0] || sok[m][1]) {
       unsigned l2 = ldy2;
-      asm volatile("" : "+s"(l2));
+      opaque_s(l2);
       char* rowp = yn + o * yslice + (unsigned)(m * G::HPM * W) * l2;
       const u32x4 v0 = *reinterpret_cast<const u32x4*>(stg_r);
       const u32x4 v1 = *reinterpret_cast<const u32x4*>(stg_r + 1024);
-      if (sok[m][0]) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + soffb), "v"(v0) : "memory");
-      if (sok[m][1]) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(rowp + step1 * l2 + soffb), "v"(v1) : "memory");
+      if (sok[m][0]) global_store_16(rowp + soffb, v0);
+      if (sok[m][1]) global_store_16(rowp + step1 * l2 + soffb, v1);
     }
   };
   for (int t = 0; t < nsteps; ++t) {
@@ -1568,7 +1496,7 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
         }
       }
 #undef M64_STEP
-      block_sync();
+      lds_barrier();
     }
     Ra = K2a; Rb = K2b; K2a = K1a; K2b = K1b; K1a = K0a; K1b = K0b;
   }
@@ -1580,11 +1508,11 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
   retire_flush(1, d1 - 1);
 
   if (stats) {
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     float* red = reinterpret_cast<float*>(smem);            // [4 waves][2][32]; the slabs are dead
     const float a = ssum + __shfl_xor(ssum, 32, 64), q2 = qsum + __shfl_xor(qsum, 32, 64);
     if (lane < 32) { red[(wave * 2 + 0) * 32 + r] = a; red[(wave * 2 + 1) * 32 + r] = q2; }
-    FPLX_LDS_BARRIER();
+    lds_barrier();
     if (tid < 64) {
       const int which = tid >> 5, c = tid & 31;
       float tt = 0.f;

@@ -9,12 +9,10 @@
 //                   the universal path (any spatial size, Cin % 16 == 0, Cout % 32 == 0).  With the
 //                   mirrored pack it is also the data-gradient kernel.
 #include "internal.h"
+#include "gfx950.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int DIRECT_THREADS = 256;
 
@@ -214,20 +212,8 @@ conv_fwd_direct(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restr
 // NDHWC image - which ds_read_b64_tr_b16 delivers for free.  The 27 taps are dealt to the 4 waves
 // (7/7/7/6), each wave keeps its taps' 32x32 fp32 tiles in registers for the whole march and
 // writes them once; a second kernel sums the per-block partials in a fixed order.
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 constexpr int WG_TH = 8;
-
-__device__ __forceinline__ bf16x8 tr_frag(const char* base_lo) {
-  // two transposed 4x16 block reads: voxels +0..3 and +4..7 (64 B per voxel row)
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo + 4 * 64));
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
 
 // one depth step of conv_wgrad_stream for wave WV: its taps WV, WV+4, ... are compile-time constants, so the
 // k-loop is straight-line code: 2 + 14 transposed reads for step ks+1 in flight behind the 7 MFMAs of step ks
@@ -605,7 +591,6 @@ inline WgCfg wg_cfg(int n, int d, int h, int w, int cin, int cout) {
 // No padding waste (every MFMA row is a real voxel), K-split only as far as needed to fill the chip, x and dy of a deep
 // level (4-8 MB) stay in L2 / Infinity Cache across the pair groups.
 constexpr int VX_KC = 128, VX_MAXW = 40, VX_XR_MAX = VX_KC + 2 * VX_MAXW + 2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4v;
 
 struct VoxGeo { int V, D, H, W, HW; unsigned mW, mH, mD; int kper, S; };   // mX = ceil(2^32 / X): q = umulhi(u, mX) for u < 2^26
 
@@ -676,11 +661,11 @@ struct VXS {
         const int combo = e >> 3, jj = e & 7, kh = combo / 3, kw = combo - 3 * kh;
         const uint64_t inv = (kh == 0 ? h0 : (kh == 2 ? h2 : 0)) | (kw == 0 ? w0 : (kw == 2 ? w2 : 0));
         const unsigned by = (unsigned)(inv >> (8 * jj)) & 0xFFu;
-        u32x4v m_;
+        u32x4 m_;
 #pragma unroll
         for (int q_ = 0; q_ < 4; ++q_)
           m_[q_] = ((by >> (2 * q_)) & 1u ? 0u : 0xFFFFu) | ((by >> (2 * q_ + 1)) & 1u ? 0u : 0xFFFF0000u);
-        *reinterpret_cast<u32x4v*>(mk_n + (combo * 16 + wv * 8 + jj) * 16) = m_;
+        *reinterpret_cast<u32x4*>(mk_n + (combo * 16 + wv * 8 + jj) * 16) = m_;
       }
     }
   }
@@ -705,7 +690,7 @@ __device__ __forceinline__ void wgrad_vox_chunk(f32x16 (&acc)[7 * COT], const ch
   // commit A + issue B | commit B | masks (A is issued at item 0); positions that exist for the 6-tap wave too
   constexpr int T_A1 = NI < 18 ? NI : 18, T_B1 = NI < 38 ? NI : 38, T_MK = NI < 42 ? NI : 42;
   bf16x8 fbw[2][COT], far[RING];
-  u32x4v mkr[RING];
+  u32x4 mkr[RING];
   uint4 st[7];
   const bool more = kn >= 0;
   char* xw_n = smem + L::X0 + (SL ^ 1) * L::X_SLOT;
@@ -715,7 +700,7 @@ __device__ __forceinline__ void wgrad_vox_chunk(f32x16 (&acc)[7 * COT], const ch
   auto load_item = [&](int t) {                        // t = ks * NT + j
     const int ks = t / NT, j = t % NT, tap = WV + 4 * j;
     far[t % RING] = tr_frag(xb[j] + XOFF + ks * 1024);
-    if (masked(j)) mkr[t % RING] = *reinterpret_cast<const u32x4v*>(mkb + MOFF + ((tap % 9) * 16 + 2 * ks) * 16);
+    if (masked(j)) mkr[t % RING] = *reinterpret_cast<const u32x4*>(mkb + MOFF + ((tap % 9) * 16 + 2 * ks) * 16);
   };
 #pragma unroll
   for (int o = 0; o < COT; ++o) fbw[0][o] = tr_frag(dyb + DOFF + o * DYPLANE);
@@ -727,7 +712,7 @@ __device__ __forceinline__ void wgrad_vox_chunk(f32x16 (&acc)[7 * COT], const ch
     if (j < COT && ks + 1 < NKS) fbw[(ks + 1) & 1][j] = tr_frag(dyb + DOFF + j * DYPLANE + (ks + 1) * 1024);
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 a = far[t % RING];
-    if (masked(j)) a = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4v, a) & mkr[t % RING]);
+    if (masked(j)) a = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a) & mkr[t % RING]);
 #pragma unroll
     for (int o = 0; o < COT; ++o)
       acc[o * 7 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, fbw[ks & 1][o], acc[o * 7 + j], 0, 0, 0);
@@ -888,12 +873,12 @@ __device__ __forceinline__ void wgrad_vox_lw_chunk(f32x16 (&acc)[7], const char*
   constexpr int XOFF = SL * L::X_SLOT, DOFF = SL * L::DY_SLOT, MOFF = SL * L::MK_SLOT;
   constexpr int PD = 3, RING = PD + 1;
   bf16x8 fbw[2], far[RING];
-  u32x4v mkr[RING];
+  u32x4 mkr[RING];
   auto masked = [](int j) { const int tap = WV + 4 * j; return ((tap / 3) % 3) != 1 || (tap % 3) != 1; };
   auto load_item = [&](int t) {
     const int ks = t / NT, j = t % NT, tap = WV + 4 * j;
     far[t % RING] = tr_frag(xb[j] + XOFF + ks * 1024);
-    if (masked(j)) mkr[t % RING] = *reinterpret_cast<const u32x4v*>(mkb + MOFF + ((tap % 9) * 16 + 2 * ks) * 16);
+    if (masked(j)) mkr[t % RING] = *reinterpret_cast<const u32x4*>(mkb + MOFF + ((tap % 9) * 16 + 2 * ks) * 16);
   };
   fbw[0] = tr_frag(dyb + DOFF);
 #pragma unroll
@@ -905,7 +890,7 @@ __device__ __forceinline__ void wgrad_vox_lw_chunk(f32x16 (&acc)[7], const char*
     if (j == 0 && ks + 1 < NKS) fbw[(ks + 1) & 1] = tr_frag(dyb + DOFF + (ks + 1) * 1024);
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 a = far[t % RING];
-    if (masked(j)) a = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4v, a) & mkr[t % RING]);
+    if (masked(j)) a = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, a) & mkr[t % RING]);
     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, fbw[ks & 1], acc[j], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -933,14 +918,14 @@ __device__ __forceinline__ void wgrad_vox_lw_compute(float* __restrict__ part, i
   for (int i = 0; i < 7; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // P0: chunk k0 sits in slot 0
+  lds_barrier();        // P0: chunk k0 sits in slot 0
   for (int kc = k0;;) {
     wgrad_vox_lw_chunk<WV, 0>(acc, xb, dyb, mkb);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     kc += VX_KC;
     if (kc >= k1) break;
     wgrad_vox_lw_chunk<WV, 1>(acc, xb, dyb, mkb);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     kc += VX_KC;
     if (kc >= k1) break;
   }
@@ -1006,22 +991,10 @@ conv_wgrad_vox_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
   const int lw = wave8 - 4;
   const bf16_t* xg = x + cit * 32;
   const bf16_t* dyg = dy + cot * 32;
-  u32x4v rx, ry;
-  rx[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xg);
-  rx[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xg >> 32) & 0xFFFFu);
-  rx[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)V * ldx * 2));
-  rx[3] = 0x00020000u;
-  ry[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)dyg);
-  ry[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)dyg >> 32) & 0xFFFFu);
-  ry[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)V * ldy * 2));
-  ry[3] = 0x00020000u;
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
-  auto buf_dma = [&](const u32x4v& rsrc, unsigned vo, unsigned dst_off) {
-    const unsigned dst = lds0 + dst_off;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(0u), "s"(dst) : "memory");
-  };
+  // (bases as integers: with the pointers hipcc orders this kernel's scalar address arithmetic differently)
+  const u32x4 rx = buffer_rsrc((size_t)xg, (int64_t)V * ldx * 2);
+  const u32x4 ry = buffer_rsrc((size_t)dyg, (int64_t)V * ldy * 2);
+  const unsigned lds0 = lds_addr(smem);
   const int nxp = (3 * XR + 15) / 16;                      // x pieces of a chunk (16 rows of 64 bytes each), then 8 dy pieces
   auto stage = [&](int kn, int slot) {
     for (int p = lw; p < nxp + VX_KC / 16; p += 4) {
@@ -1034,11 +1007,11 @@ conv_wgrad_vox_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
         const unsigned c = vc[in ? t : 0];
         const bool ok = in && c != 0xFFu && !((pl == 0 && (c & 2u)) || (pl == 2 && (c & 1u)));
         const unsigned vo = ok ? (unsigned)(((int64_t)u * ldx + (lane & 3) * 8) * 2) : 0x80000000u;
-        if (rr < 3 * XR) buf_dma(rx, vo, (unsigned)(L::X0 + slot * L::X_SLOT + p * 1024));      // (rows past the planes: not written)
+        if (rr < 3 * XR) lds_dma_buffer(rx, vo, 0u, lds0 + (unsigned)(L::X0 + slot * L::X_SLOT + p * 1024));      // (rows past the planes: not written)
       } else {
         const int v_ = kn + (p - nxp) * 16 + (lane >> 2);
         const unsigned vo = v_ < k1 ? (unsigned)(((int64_t)v_ * ldy + (lane & 3) * 8) * 2) : 0x80000000u;
-        buf_dma(ry, vo, (unsigned)(L::DY0 + slot * L::DY_SLOT + (p - nxp) * 1024));
+        lds_dma_buffer(ry, vo, 0u, lds0 + (unsigned)(L::DY0 + slot * L::DY_SLOT + (p - nxp) * 1024));
       }
     }
     if (lw < 2) {                                          // the chunk's masks (VXS::masks): wave lw takes 64 voxels
@@ -1052,23 +1025,23 @@ conv_wgrad_vox_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __res
           const int combo = e >> 3, jj = e & 7, kh = combo / 3, kw = combo - 3 * kh;
           const uint64_t inv = (kh == 0 ? h0 : (kh == 2 ? h2 : 0)) | (kw == 0 ? w0 : (kw == 2 ? w2 : 0));
           const unsigned by = (unsigned)(inv >> (8 * jj)) & 0xFFu;
-          u32x4v m_;
+          u32x4 m_;
 #pragma unroll
           for (int q_ = 0; q_ < 4; ++q_)
             m_[q_] = ((by >> (2 * q_)) & 1u ? 0u : 0xFFFFu) | ((by >> (2 * q_ + 1)) & 1u ? 0u : 0xFFFF0000u);
-          *reinterpret_cast<u32x4v*>(mk_n + (combo * 16 + lw * 8 + jj) * 16) = m_;
+          *reinterpret_cast<u32x4*>(mk_n + (combo * 16 + lw * 8 + jj) * 16) = m_;
         }
       }
     }
   };
   stage(k0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // P0
+  wait_vmcnt0();
+  lds_barrier();        // P0
   for (int kc = k0, slot = 0;; slot ^= 1) {
     const int kn = kc + VX_KC;
     if (kn < k1) stage(kn, slot ^ 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_vmcnt0();
+    lds_barrier();
     kc = kn;
     if (kc >= k1) break;
   }
@@ -1653,7 +1626,7 @@ conv_fwd_stream(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restr
     }
     if (d + 1 < d1) {
       // one barrier publishes the new slab; raw (no fence): the output stores stay in flight across it
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      lds_barrier();
     }
   }
   if (stats) {
@@ -1989,8 +1962,6 @@ splitk_finish_k(const float* __restrict__ partial, int ks, int64_t V, int Cout, 
 // follows ds_read_b128's lane groups (pswz below: conflict-free fragment reads since round 6).  The product is TRANSPOSED,
 // D[ci][parent] = Wb[ci][k] dy^T[k][parent]: the weights are the A operand and stay in registers for the whole kernel, a lane
 // ends up with 16 input channels of ONE parent, two v_permlane32_swap exchanges make them two 16-byte stores.
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2d;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4d;
 template <int CO32, int NTW>       // Cout / 32 (1 | 2), Cin / 32 (2 | 4): four wave tiles = (4 / NTW) parent tiles x NTW channel tiles
 __global__ void __launch_bounds__(256)
 deconv_dgrad_rows(const bf16_t* __restrict__ dy, int64_t ldy, const bf16_t* __restrict__ wb, bf16_t* __restrict__ dx,
@@ -2081,15 +2052,15 @@ deconv_dgrad_rows(const bf16_t* __restrict__ dy, int64_t ldy, const bf16_t* __re
     for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const u32x2d sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
+        const u32x2 sw = __builtin_amdgcn_permlane32_swap(pk[4 * g2 + e], pk[4 * g2 + 2 + e], false, false);
         pk[4 * g2 + e] = sw[0];
         pk[4 * g2 + 2 + e] = sw[1];
       }
     const int wv = g.w0 + mt * 32 + r;
     if (wv < W) {
       bf16_t* dst = dx + ((((int64_t)g.n * D + g.d) * H + g.h) * W + wv) * ldx + n0 + 8 * kq;
-      *reinterpret_cast<u32x4d*>(dst) = u32x4d{pk[0], pk[1], pk[2], pk[3]};
-      *reinterpret_cast<u32x4d*>(dst + 16) = u32x4d{pk[4], pk[5], pk[6], pk[7]};
+      *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+      *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
     }
   }
 }

@@ -20,17 +20,12 @@
 //     the hardware's out-of-range zeros, the per-lane offsets are constants of the march, the depth is the scalar offset;
 //     no staging registers, no commit phase, a 4-slot x ring + 2-slot dy ring.
 #include "internal.h"
+#include "gfx950.h"
 #include <stdlib.h>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Wint-to-pointer-cast"      // LDS pointers are 32 bits wide: they are formed from 32-bit addresses
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 // MB: the step's one barrier sits in the MIDDLE of the step and the rings get one x slot and one dy slot more (5 + 3): the DMA
 // of a slab is issued behind the barrier of the step BEFORE the one whose barrier publishes it, into a slot nobody has read
@@ -51,20 +46,11 @@ struct WR {
   static constexpr int XPW = (XP + 3) / 4, YPW = (YP + 3) / 4;   // pieces per wave
 };
 
-// fragment reads take 32-bit LDS byte addresses: an opaque per-step base (one VGPR per slab, see lds_base) + a compile-time
-// offset that lands in the instruction's 16-bit offset field
-__device__ __forceinline__ bf16x8 tr_frag(unsigned base_lo) {
-  // two transposed 4 x 16 block reads: voxels +0..3 and +4..7 of a lane group's 8 (64 bytes per voxel row)
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base_lo + 4 * 64));
-  bf16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
+// fragment reads (tr_frag) take 32-bit LDS byte addresses: an opaque per-step base (one VGPR per slab, see lds_base) + a
+// compile-time offset that lands in the instruction's 16-bit offset field
 // hipcc must not take a base apart and hoist base + constant sums out of the depth loop (it did: 30 address registers)
 __device__ __forceinline__ unsigned lds_base(unsigned a) {
-  asm volatile("" : "+v"(a));
+  opaque_v(a);
   return a;
 }
 
@@ -120,37 +106,25 @@ __device__ __forceinline__ void roll_march(const bf16_t* __restrict__ x, int64_t
   // the two ci tiles of a split concatenation (x1 != NULL, Cin = 64) come from two tensors
   const char* xn = reinterpret_cast<const char*>((x1 && cg == 1) ? x1 : x + cg * 32) + (int64_t)n * D * xslice;
   const char* yn = reinterpret_cast<const char*>(dy + cot * 32) + (int64_t)n * D * yslice;
-  u32x4 xr, yr;
-  xr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
-  xr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
-  xr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * xslice - (ldx - 32) * 2));
-  xr[3] = 0x00020000u;
-  yr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)yn);
-  yr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)yn >> 32) & 0xFFFFu);
-  yr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * yslice - (ldy - 32) * 2));
-  yr[3] = 0x00020000u;
+  const u32x4 xr = buffer_rsrc(xn, (int64_t)D * xslice - (ldx - 32) * 2);
+  const u32x4 yr = buffer_rsrc(yn, (int64_t)D * yslice - (ldy - 32) * 2);
   const unsigned xslice32 = __builtin_amdgcn_readfirstlane((unsigned)xslice);
   const unsigned yslice32 = __builtin_amdgcn_readfirstlane((unsigned)yslice);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
-  auto dma = [&](const u32x4& rsrc, unsigned vo, unsigned so, unsigned dst) {    // dst: LDS byte address of the 1-KiB piece
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so), "s"(dst) : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem);
   // x slab of depth d0 - 1 + m lives in slot m & 3, the dy slab of depth d0 + t in slot t & 1
   // on = false (nothing follows this block's last depth): the scalar offset is out of range, the slot - a free one - gets zeros
   auto dma_x = [&](int m, int k, bool on) {            // piece WV + 4 k of slab m
     if (WV + 4 * k < G::XP) {
       const int s = d0 - 1 + m;
       const unsigned so = __builtin_amdgcn_readfirstlane((on && s >= 0 && s < D) ? (unsigned)s * xslice32 : 0x40000000u);
-      dma(xr, xvo[k], so, lds0 + (unsigned)(((unsigned)m % G::NXS) * G::XSLOT + (WV + 4 * k) * 1024));
+      lds_dma_buffer(xr, xvo[k], so, lds0 + (unsigned)(((unsigned)m % G::NXS) * G::XSLOT + (WV + 4 * k) * 1024));
     }
   };
   auto dma_y = [&](int t, int k, bool on) {
     if (WV + 4 * k < G::YP) {
       const int s = d0 + t;
       const unsigned so = __builtin_amdgcn_readfirstlane((on && s < D) ? (unsigned)s * yslice32 : 0x40000000u);
-      dma(yr, yvo[k], so, lds0 + (unsigned)(G::NXS * G::XSLOT + ((unsigned)t % G::NYS) * G::YSLOT + (WV + 4 * k) * 1024));
+      lds_dma_buffer(yr, yvo[k], so, lds0 + (unsigned)(G::NXS * G::XSLOT + ((unsigned)t % G::NYS) * G::YSLOT + (WV + 4 * k) * 1024));
     }
   };
 
@@ -176,7 +150,7 @@ __device__ __forceinline__ void roll_march(const bf16_t* __restrict__ x, int64_t
 #pragma unroll
     for (int k = 0; k < G::YPW; ++k) dma_y(1, k, nd > 1);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt0();
   __builtin_amdgcn_s_barrier();
 
   bf16x8 fx[2][3];       // [cell parity][triple 0, triple 1, single]
@@ -239,16 +213,16 @@ __device__ __forceinline__ void roll_march(const bf16_t* __restrict__ x, int64_t
         __builtin_amdgcn_sched_barrier(0);
       }
       if (G::MB && k == PB - 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt0();
         __builtin_amdgcn_s_barrier();
       }
     }
     if (!G::MB) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt0();
       __builtin_amdgcn_s_barrier();
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt0();
 
   // partial tiles: part[block][pair][tap][co][ci] - a lane owns 4 consecutive ci per register quad: 16-byte stores
   const int co = lane & 31, rbase = (lane >> 5) * 4;
@@ -286,7 +260,6 @@ struct WR16 {
   static constexpr int XPW = (XP + 3) / 4, YPW = (YP + 3) / 4;
 };
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <class G, int WV>
 __device__ __forceinline__ void roll16_march(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ dy,
@@ -329,30 +302,18 @@ __device__ __forceinline__ void roll16_march(const bf16_t* __restrict__ x, int64
   const int64_t xslice = (int64_t)H * W * ldx * 2, yslice = (int64_t)H * W * ldy * 2;
   const char* xn = reinterpret_cast<const char*>((x1 && cg == 1) ? x1 : x + cg * 32) + (int64_t)n * D * xslice;
   const char* yn = reinterpret_cast<const char*>(dy + cot * 32) + (int64_t)n * D * yslice;
-  u32x4 xr, yr;
-  xr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
-  xr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
-  xr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * xslice - (ldx - 32) * 2));
-  xr[3] = 0x00020000u;
-  yr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)yn);
-  yr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)yn >> 32) & 0xFFFFu);
-  yr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * yslice - (ldy - 32) * 2));
-  yr[3] = 0x00020000u;
+  const u32x4 xr = buffer_rsrc(xn, (int64_t)D * xslice - (ldx - 32) * 2);
+  const u32x4 yr = buffer_rsrc(yn, (int64_t)D * yslice - (ldy - 32) * 2);
   const unsigned xslice32 = __builtin_amdgcn_readfirstlane((unsigned)xslice);
   const unsigned yslice32 = __builtin_amdgcn_readfirstlane((unsigned)yslice);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
-  auto dma = [&](const u32x4& rsrc, unsigned vo, unsigned so, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so), "s"(dst) : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem);
   auto dma_x = [&](int m, int k, bool on) {
     if (WV + 4 * k < G::XP) {
       constexpr int dummy = 0; (void)dummy;
       const int P = WV + 4 * k;
       const int s = d0 - 1 + m;
       const unsigned so = __builtin_amdgcn_readfirstlane((on && s >= 0 && s < D) ? (unsigned)s * xslice32 : 0x40000000u);
-      dma(xr, xvo[k], so, lds0 + (unsigned)(((unsigned)m % G::NXS) * G::XSLOT + (P & 1) * G::XPLANE + (P >> 1) * 1024));
+      lds_dma_buffer(xr, xvo[k], so, lds0 + (unsigned)(((unsigned)m % G::NXS) * G::XSLOT + (P & 1) * G::XPLANE + (P >> 1) * 1024));
     }
   };
   auto dma_y = [&](int t, int k, bool on) {
@@ -360,7 +321,7 @@ __device__ __forceinline__ void roll16_march(const bf16_t* __restrict__ x, int64
       const int P = WV + 4 * k;
       const int s = d0 + t;
       const unsigned so = __builtin_amdgcn_readfirstlane((on && s < D) ? (unsigned)s * yslice32 : 0x40000000u);
-      dma(yr, yvo[k], so, lds0 + (unsigned)(G::NXS * G::XSLOT + ((unsigned)t % G::NYS) * G::YSLOT + (P & 1) * G::YPLANE + (P >> 1) * 1024));
+      lds_dma_buffer(yr, yvo[k], so, lds0 + (unsigned)(G::NXS * G::XSLOT + ((unsigned)t % G::NYS) * G::YSLOT + (P & 1) * G::YPLANE + (P >> 1) * 1024));
     }
   };
 
@@ -383,17 +344,13 @@ __device__ __forceinline__ void roll16_march(const bf16_t* __restrict__ x, int64
 #pragma unroll
     for (int k = 0; k < G::YPW; ++k) dma_y(1, k, nd > 1);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt0();
   __builtin_amdgcn_s_barrier();
 
   // a fragment = 16 channels x 32 voxels: two transposed reads of 512 contiguous bytes (voxels +0..15 and +16..31 of the plane)
   auto frag = [&](unsigned pl) {
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pl));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pl + 16 * 32));
-    bf16x8 r;
-    r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-    r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-    return r;
+    return tr_splice(__builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pl)),
+                     __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(pl + 16 * 32)));
   };
   bf16x8 fx[2][3][2];    // [cell parity][triple 0, triple 1, single][ci half]
   bf16x8 fy[4][2];       // dy rows (ring by row & 3) x co half
@@ -460,16 +417,16 @@ __device__ __forceinline__ void roll16_march(const bf16_t* __restrict__ x, int64
         __builtin_amdgcn_sched_barrier(0);
       }
       if (G::MB && rx == PB - 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt0();
         __builtin_amdgcn_s_barrier();
       }
     }
     if (!G::MB) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt0();
       __builtin_amdgcn_s_barrier();
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt0();
 
   // partial tiles [tap][co][ci]: block (a, b) of a lane = ci 16 a + 4 (lane / 16) .. + 3 at co 16 b + lane % 16: one 16-byte store
   const int pair = cot * ncg + cg;
@@ -573,23 +530,11 @@ __device__ __forceinline__ void roll2d_march(const bf16_t* __restrict__ x, int64
   const int64_t xslice = (int64_t)H * W * ldx * 2, yslice = (int64_t)H * W * ldy * 2;
   const char* xn = reinterpret_cast<const char*>((x1 && cg == 1) ? x1 : x + cg * 32) + (int64_t)n * D * xslice;
   const char* yn = reinterpret_cast<const char*>(dy + cot * 32) + (int64_t)n * D * yslice;
-  u32x4 xr, yr;
-  xr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)xn);
-  xr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)xn >> 32) & 0xFFFFu);
-  xr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * xslice - (ldx - 32) * 2));
-  xr[3] = 0x00020000u;
-  yr[0] = __builtin_amdgcn_readfirstlane((unsigned)(size_t)yn);
-  yr[1] = __builtin_amdgcn_readfirstlane((unsigned)((size_t)yn >> 32) & 0xFFFFu);
-  yr[2] = __builtin_amdgcn_readfirstlane((unsigned)((int64_t)D * yslice - (ldy - 32) * 2));
-  yr[3] = 0x00020000u;
+  const u32x4 xr = buffer_rsrc(xn, (int64_t)D * xslice - (ldx - 32) * 2);
+  const u32x4 yr = buffer_rsrc(yn, (int64_t)D * yslice - (ldy - 32) * 2);
   const unsigned xslice32 = __builtin_amdgcn_readfirstlane((unsigned)xslice);
   const unsigned yslice32 = __builtin_amdgcn_readfirstlane((unsigned)yslice);
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((__attribute__((address_space(3))) char*)smem));
-  auto dma = [&](const u32x4& rsrc, unsigned vo, unsigned so, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(vo), "s"(rsrc), "s"(so), "s"(dst) : "memory");
-  };
+  const unsigned lds0 = lds_addr(smem);
   const int nd = d1 - d0;
   // piece j of this wave for the slabs of depth d0 + t (ring slot t % 3); off (t >= nd): out of range, the free slot gets zeros
   auto issue = [&](int t, int j) {
@@ -598,16 +543,16 @@ __device__ __forceinline__ void roll2d_march(const bf16_t* __restrict__ x, int64
     if (j < G::XPW) {
       const int piece = WV + 4 * j < G::XP ? WV + 4 * j : G::XP - 1;
       const unsigned so = __builtin_amdgcn_readfirstlane(on ? (unsigned)(d0 + t) * xslice32 : 0x40000000u);
-      dma(xr, xvo[j], so, lds0 + slot * G::XSLOT + piece * 1024);
+      lds_dma_buffer(xr, xvo[j], so, lds0 + slot * G::XSLOT + piece * 1024);
     } else {
       const int jj = j - G::XPW;
       const int piece = WV + 4 * jj < G::YP ? WV + 4 * jj : G::YP - 1;
       const unsigned so = __builtin_amdgcn_readfirstlane(on ? (unsigned)(d0 + t) * yslice32 : 0x40000000u);
-      dma(yr, yvo[jj], so, lds0 + G::NS * G::XSLOT + slot * G::YSLOT + piece * 1024);
+      lds_dma_buffer(yr, yvo[jj], so, lds0 + G::NS * G::XSLOT + slot * G::YSLOT + piece * 1024);
     }
   };
   auto wait_newest = [&]() {                               // all but the NPW pieces issued last have landed
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(G::NPW) : "memory");
+    wait_vmcnt<G::NPW>();
     __builtin_amdgcn_s_barrier();
   };
 
@@ -657,7 +602,7 @@ __device__ __forceinline__ void roll2d_march(const bf16_t* __restrict__ x, int64
     }
     wait_newest();
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt0();
 
   if (WV < 3) {
     const int co = lane & 31, rbase = (lane >> 5) * 4;

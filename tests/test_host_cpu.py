@@ -338,3 +338,27 @@ def test_dispatch_plan_matches_parent(golden_dir):
         assert len(want) == len(grid) == len(got[kn])
         for g, a, b in zip(grid, got[kn], want):
             assert a == b, (kn, g, [(c, x, y) for c, x, y in zip(mg.COLUMNS, a, b) if x != y])
+
+
+def test_device_primitives_live_in_the_device_header_only():
+    """The kernels' inline-asm sequences and vector types are defined once, in csrc/gfx950.h: no .hip file contains the token
+    `asm`, and none (and no other header) introduces one of the vector type names by typedef or using.  A kernel file copied
+    from another must include the header, not bring its own copies back.  (No site had to stay inline: no exception.)"""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fpl-plus_amd", "csrc")
+    hips = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(hips) >= 15
+    names = "bf16x8|bf16x4|f32x16|f32x4|f32x2|u32x4|u32x2|lds_bf16x4"
+    intro = re.compile(r"\btypedef\b[^;]*\b(%s)\s*;|\busing\s+(%s)\s*=" % (names, names))
+    for path in hips + sorted(glob.glob(os.path.join(csrc, "*.h"))):
+        src = open(path).read()
+        base = os.path.basename(path)
+        found = sorted({a or b for a, b in intro.findall(src)})
+        if base == "gfx950.h":
+            assert found == sorted(names.split("|")), found
+            continue
+        assert not found, (base, found)
+        if base.endswith(".hip"):
+            lines = [i + 1 for i, l in enumerate(src.splitlines()) if re.search(r"\basm\b|\b__asm__?\b", l)]
+            assert not lines, (base, lines)
