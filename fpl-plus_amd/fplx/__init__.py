@@ -11,7 +11,8 @@ _lib.lib()          # fail loudly, now, if the HIP extension is missing
 from .net import UNet2D5_dsbn                                      # noqa: E402
 from .dsbn import DomainSpecificBatchNorm3d                        # noqa: E402
 from .loss import (SegLossDict, DiceLoss, CrossEntropyLoss, DiceLoss_weight, CombinedLoss,  # noqa: E402
-                   EntropyTerm, make_loss)
+                   EntropyTerm, make_loss, SegLossDictAll, FocalDiceLoss, NoiseRobustDiceLoss, ExpLogLoss,
+                   GeneralizedCELoss, MAELoss, MSELoss, SLSRLoss)
 from .infer import Inferer                                         # noqa: E402
 from .agent import SegmentationAgent, SegNetDict                   # noqa: E402
 from .optim import FusedAdam, get_optimizer, get_lr_scheduler      # noqa: E402
@@ -25,4 +26,5 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
            "SegmentationAgent", "FusedAdam", "get_optimizer", "get_lr_scheduler", "TrainStep",
            "parse_config", "synchronize_config", "filter", "ops", "ddp", "transform", "nifti", "evaluation", "NiftyDataset",
-           "postprocess", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]
+           "postprocess", "SegLossDictAll", "FocalDiceLoss", "NoiseRobustDiceLoss", "ExpLogLoss", "GeneralizedCELoss", "MAELoss",
+           "MSELoss", "SLSRLoss", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]

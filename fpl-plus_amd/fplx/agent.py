@@ -35,7 +35,7 @@ from .infer import Inferer
 from .nifti import save_array_as_nifty_volume
 from .postprocess import PostProcessDict
 from .transform import TransformDict, Compose
-from .loss import SegLossDict, make_loss
+from .loss import SegLossDict, SegLossDictAll, make_loss
 from .net import UNet2D5_dsbn
 from .optim import get_optimizer, get_lr_scheduler
 
@@ -198,7 +198,7 @@ class SegmentationAgent(object):
 
     def create_loss_calculator(self, entropy_weight=0.0):
         if self.loss_dict is None:
-            self.loss_dict = SegLossDict
+            self.loss_dict = SegLossDictAll
         self.loss_calculator = make_loss(self.config['training'], self.loss_dict, entropy_weight)
         if self.distributed:
             self.loss_calculator.dist_sync = True                 # ONE loss over the full batch of all ranks
@@ -245,9 +245,9 @@ class SegmentationAgent(object):
         if not ok:
             self._ts = None
             return None
-        key = (id(net), id(opt), tuple(lc.terms), bool(lc.softmax))
+        key = (id(net), id(opt), tuple(lc.terms), bool(lc.softmax), lc.ext_spec())
         if self._ts is None or self._ts_key != key:
-            self._ts = TrainStep(net, lc.terms, lc.softmax, optimizer=opt)
+            self._ts = TrainStep(net, lc.terms, lc.softmax, optimizer=opt, loss_ext=lc.ext_spec())
             self._ts_key = key
         return self._ts
 

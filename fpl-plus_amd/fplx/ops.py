@@ -459,6 +459,78 @@ def seg_loss_bwd(logits, label, pw, coef, gscale, weights, softmax, dlogits):
          weights[1], weights[2], weights[3], 1 if softmax else 0, ptr(dlogits), stream())
 
 
+# ---- second loss family (include/fplx.h, "segmentation loss, second family")
+LOSS_EXT_TERMS = ("focal", "noise_robust", "explog", "gce", "mae", "mse", "slsr")        # order of cfg[4..10] and of out[4 + C ..]
+LOSS_EXT_PARAMS = ("beta", "gamma_nr", "w_dice_el", "gamma_el", "q", "epsilon", "use_pixel_weight", "class_weight")
+LOSS_EXT_DEFAULTS = (1.0, 1.0, 0.5, 1.0, 0.5, 0.25, False, None)
+
+
+def loss_ext_k(c):
+    return 10 * c + 7
+
+
+def loss_ext_nout(c):
+    return 4 + c + 7
+
+
+def loss_ext_ncoef(n, c):
+    return n * c * 2 + 2 + 4 * c + 4
+
+
+def loss_ext_cfg(terms, ext, c):
+    """the host array `cfg` of the fplx_seg_loss_ext_* calls: terms = the four weights of the first family, ext = (the seven
+    weights in LOSS_EXT_TERMS order, the parameters in LOSS_EXT_PARAMS order); class_weight None = all ones"""
+    w, prm = ext
+    if len(terms) != 4 or len(w) != len(LOSS_EXT_TERMS) or len(prm) != len(LOSS_EXT_PARAMS):
+        raise ValueError("fplx loss: malformed term description")
+    cw = prm[7]
+    if cw is None:
+        cw = (1.0,) * c
+    if len(cw) != c:
+        raise ValueError("fplx loss: loss_class_weight has {0:} entries for {1:} classes".format(len(cw), c))
+    vals = [float(t) for t in terms] + [float(t) for t in w] + [float(t) for t in prm[:6]] + [1.0 if prm[6] else 0.0]
+    vals += [float(t) for t in cw]
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+def seg_loss_ext_fwd(logits, label, pw, iw, cfg, softmax, part, out, coef):
+    n, c = logits.shape[0], logits.shape[1]
+    v = logits[0, 0].numel()
+    call("fplx_seg_loss_ext_fwd", ptr(logits), ptr(label), ptr(pw), ptr(iw), n, c, v, cfg, 1 if softmax else 0, ptr(part),
+         ptr(out), ptr(coef), stream())
+
+
+def seg_loss_ext_sums(logits, label, pw, cfg, softmax, part, sums, totals):
+    n, c = logits.shape[0], logits.shape[1]
+    v = logits[0, 0].numel()
+    call("fplx_seg_loss_ext_sums", ptr(logits), ptr(label), ptr(pw), n, c, v, cfg, 1 if softmax else 0, ptr(part), ptr(sums),
+         ptr(totals), stream())
+
+
+def seg_loss_ext_from_sums(sums, totals, iw, n, n_global, c, v, has_pw, cfg, out, coef):
+    call("fplx_seg_loss_ext_from_sums", ptr(sums), ptr(totals), ptr(iw), n, n_global, c, v, 1 if has_pw else 0, cfg, ptr(out),
+         ptr(coef), stream())
+
+
+def seg_loss_ext_fwd_dist(logits, label, pw, iw, cfg, softmax, part, out, coef, group):
+    """seg_loss_ext_fwd under data parallelism, as seg_loss_fwd_dist: every new sum is additive over the ranks"""
+    import torch.distributed as dist
+    n, c = logits.shape[0], logits.shape[1]
+    v = logits[0, 0].numel()
+    sums = torch.empty((n + 1, loss_ext_k(c)), dtype=torch.float64, device=logits.device)
+    seg_loss_ext_sums(logits, label, pw, cfg, softmax, part, sums[:n], sums[n])
+    dist.all_reduce(sums[n], op=dist.ReduceOp.SUM, group=group)
+    world = dist.get_world_size(group)
+    seg_loss_ext_from_sums(sums[:n], sums[n], iw, n, n * world, c, v, pw is not None, cfg, out, coef)
+
+
+def seg_loss_ext_bwd(logits, label, pw, coef, gscale, cfg, softmax, dlogits):
+    n, c = logits.shape[0], logits.shape[1]
+    v = logits[0, 0].numel()
+    call("fplx_seg_loss_ext_bwd", ptr(logits), ptr(label), ptr(pw), ptr(coef), ptr(gscale), n, c, v, cfg, 1 if softmax else 0,
+         ptr(dlogits), stream())
+
+
 def adam_step(p, g, m, v, lr, step, weight_decay, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
     call("fplx_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay,
          int(step), grad_scale, stream())

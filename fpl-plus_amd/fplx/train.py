@@ -16,8 +16,9 @@ from .optim import FusedAdam
 
 class TrainStep(object):
     def __init__(self, net, loss_terms=(1.0, 0.0, 0.0, 0.0), softmax=True, lr=1e-4, weight_decay=1e-5,
-                 milestones=(), gamma=0.5, group=None, bucket_elems=1 << 21, optimizer=None):
-        """optimizer: an existing fplx.FusedAdam over `net` (SegmentationAgent routes its training loops through this class and
+                 milestones=(), gamma=0.5, group=None, bucket_elems=1 << 21, optimizer=None, loss_ext=None):
+        """loss_ext: terms of the second loss family, as AbstractSegLoss.ext_spec() gives them (None: the first family's pass);
+        optimizer: an existing fplx.FusedAdam over `net` (SegmentationAgent routes its training loops through this class and
         keeps ITS optimiser - state, param_groups, the torch lr scheduler stepping it); its learning rate is then whatever the
         param_group says at the time of the step, `lr` / `milestones` / `gamma` are not used."""
         net._ensure_flat()
@@ -25,6 +26,7 @@ class TrainStep(object):
         self.net = net
         self.terms = tuple(float(t) for t in loss_terms)
         self.softmax = bool(softmax)
+        self.loss_ext = loss_ext
         self.external_lr = optimizer is not None
         self.opt = optimizer if optimizer is not None else FusedAdam(net, lr, weight_decay=weight_decay)
         self.base_lr, self.milestones, self.gamma = lr, sorted(milestones), gamma
@@ -51,10 +53,26 @@ class TrainStep(object):
     def _loss_buffers(self, n, c, v, dev):
         key = (n, c, v)
         if key not in self._loss_bufs:
+            k, ncoef = (ops.loss_k(c), n * c * 2 + 2) if self.loss_ext is None else (ops.loss_ext_k(c), ops.loss_ext_ncoef(n, c))
             self._loss_bufs[key] = (
-                torch.empty((n, ops.loss_rows(v), ops.loss_k(c)), dtype=torch.float32, device=dev),
-                torch.empty(n * c * 2 + 2, dtype=torch.float32, device=dev))
+                torch.empty((n, ops.loss_rows(v), k), dtype=torch.float32, device=dev),
+                torch.empty(ncoef, dtype=torch.float32, device=dev))
         return self._loss_bufs[key]
+
+    def _loss_ext(self, logits, label, pw, iw, gscale, part, coef):
+        """the loss and its gradient through the second family's pass -> (out, dlogits)"""
+        from .loss import check_ext_inputs
+        check_ext_inputs(self.loss_ext, pw)
+        c = logits.shape[1]
+        cfg = ops.loss_ext_cfg(self.terms, self.loss_ext, c)
+        out = torch.empty(ops.loss_ext_nout(c), dtype=torch.float32, device=logits.device)
+        if self.dist_loss:
+            ops.seg_loss_ext_fwd_dist(logits, label, pw, iw, cfg, self.softmax, part, out, coef, self.group)
+        else:
+            ops.seg_loss_ext_fwd(logits, label, pw, iw, cfg, self.softmax, part, out, coef)
+        dlogits = torch.empty_like(logits)
+        ops.seg_loss_ext_bwd(logits, label, pw, coef, gscale, cfg, self.softmax, dlogits)
+        return out, dlogits
 
     def _fwd_bwd(self, x, label, domain, pw, iw, gscale, gflat, reduce_hook, reuse_packs=False):
         net = self.net
@@ -79,6 +97,10 @@ class TrainStep(object):
         if iw is not None:
             iw = iw.float().contiguous()
         part, coef = self._loss_buffers(n, c, v, logits.device)
+        if self.loss_ext is not None:
+            out, dlogits = self._loss_ext(logits, label, pw, iw, gscale, part, coef)
+            net.engine.backward(sv, dlogits, gflat, reduce_hook)
+            return out
         out = torch.empty(4 + c, dtype=torch.float32, device=logits.device)
         if self.dist_loss:
             ops.seg_loss_fwd_dist(logits, label, pw, iw, self.terms, self.softmax, part, out, coef, self.group)

@@ -391,6 +391,52 @@ int fplx_seg_loss_bwd(const float* logits, const float* label, const float* pixe
                       float w_dice, float w_ce, float w_dice_img, float w_entropy, int softmax,
                       float* dlogits, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ segmentation loss, second family
+ * The seven remaining losses of the reference's SegLossDict (loss/loss_dict_seg.py:31-41) fused with the four terms above:
+ * FocalDice (dice.py:147-161), NoiseRobustDice (dice.py:181-199), ExpLog (exp_log.py:29-56), GeneralizedCE (ce.py:68-93),
+ * MAE / MSE (mse.py) and SLSR (slsr.py:34-58).  ONE forward pass over logits, label and pixel_weight makes the 6C + 3 sums of
+ * the first family (same positions) and the new ones behind them; ONE backward pass writes dlogits for any mixture.  Tensors,
+ * `softmax`, `part` (rows = fplx_loss_rows, K = FPLX_LOSS_EXT_K(C)), image_weight, gscale and the data-parallel split
+ * (sums -> all-reduce of totals -> from_sums with n_global) are as above.
+ *   cfg    HOST floats [FPLX_LOSS_EXT_NCFG(C)], read during the call (the caller may reuse the array at once):
+ *            [0..3]   w_dice, w_ce, w_dice_img, w_entropy            the first family's term weights
+ *            [4..10]  w_focal, w_noise_robust, w_explog, w_gce, w_mae, w_mse, w_slsr
+ *            [11]     beta        FocalDiceLoss_beta
+ *            [12]     gamma_nr    NoiseRobustDiceLoss_gamma
+ *            [13]     w_dice_el   ExpLogLoss_w_dice
+ *            [14]     gamma_el    ExpLogLoss_gamma
+ *            [15]     q           loss_gce_q
+ *            [16]     epsilon     slsrloss_epsilon
+ *            [17]     use_pixel_weight (0 / 1)  GeneralizedCE weights by pixel_weight and divides by its sum (no epsilon);
+ *                     pixel_weight must then be given (FPLX_E_NULL otherwise)
+ *            [18..18+C-1]  GeneralizedCE class weights (all 1 for none)
+ *          A term whose weight is 0 is not evaluated in the voxel loops.
+ *   What pixel_weight means per term, as in the reference: Dice / CE / image-weighted Dice weight by it; FocalDice,
+ *   NoiseRobustDice, ExpLog, MAE and MSE ignore it; SLSR reads it as a mask (> 0: the label is smoothed); GeneralizedCE uses
+ *   it only with cfg[17].
+ *   sums / totals: double [N][K] / [K], K = FPLX_LOSS_EXT_K(C): [0, 6C + 3) as FPLX_LOSS_K; then per class c four entries at
+ *          6C + 3 + 4c: sum p, sum y p (both unweighted), sum |p - y|^gamma_nr, sum y (-log(0.005 + 0.99 p))^gamma_el; then at
+ *          10C + 3: the GeneralizedCE numerator, sum (p - y)^2, sum |p - y|, the SLSR numerator.
+ *   out    fp32 device [FPLX_LOSS_EXT_NOUT(C)]: [0] total of all eleven terms, [1..3] and [4, 4 + C) as above, then the values
+ *          of FocalDice, NoiseRobustDice, ExpLog, GeneralizedCE, MAE, MSE, SLSR (unweighted).
+ *   coef   fp32 device [FPLX_LOSS_EXT_NCOEF(N, C)] */
+#define FPLX_LOSS_EXT_K(C) (10 * (C) + 7)
+#define FPLX_LOSS_EXT_NCFG(C) (18 + (C))
+#define FPLX_LOSS_EXT_NOUT(C) (4 + (C) + 7)
+#define FPLX_LOSS_EXT_NCOEF(N, C) ((N) * (C) * 2 + 2 + 4 * (C) + 4)
+int fplx_seg_loss_ext_fwd(const float* logits, const float* label, const float* pixel_weight, const float* image_weight,
+                          int n, int c, int64_t voxels_per_sample, const float* cfg, int softmax, float* part, float* out,
+                          float* coef, fplx_stream_t stream);
+int fplx_seg_loss_ext_sums(const float* logits, const float* label, const float* pixel_weight, int n, int c,
+                           int64_t voxels_per_sample, const float* cfg, int softmax, float* part, double* sums,
+                           double* totals, fplx_stream_t stream);
+int fplx_seg_loss_ext_from_sums(const double* sums, const double* totals, const float* image_weight, int n, int n_global,
+                                int c, int64_t voxels_per_sample, int has_pixel_weight, const float* cfg, float* out,
+                                float* coef, fplx_stream_t stream);
+int fplx_seg_loss_ext_bwd(const float* logits, const float* label, const float* pixel_weight, const float* coef,
+                          const float* gscale, int n, int c, int64_t voxels_per_sample, const float* cfg, int softmax,
+                          float* dlogits, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser
  * torch.optim.Adam(lr, weight_decay) as built by net_run_dsbn/get_optimizer.py:17 on a flat
  * fp32 buffer: g += wd*p; m,v moments; bias correction with `step` (1-based); p -= lr/bc1 * m/(sqrt(v)/sqrt(bc2)+eps).
