@@ -1,6 +1,7 @@
 // Shared helpers for the fplx HIP kernels (gfx950 only: wave = 64 lanes).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -77,6 +78,149 @@ __device__ __forceinline__ void fplx_adam_elem(float& pi, float g, float& mi, fl
   vi = fmaf(c.b2, vi, (c.omb2 * gi) * gi);
   const float denom = fmaf(sqrtf(vi), c.inv_sqrt_bc2, c.eps);
   pi = fmaf(-c.step_size, mi / denom, pi);
+}
+// one element of the reference's seven other optimisers (get_optimizer.py:13-34, torch's _single_tensor_* functions) - shared by
+// optim_k (elementwise.hip) and optim_pack27_multi (conv_generic.hip) under the same rule as fplx_adam_elem: every addition
+// that takes a product is an explicit fma, and every product that feeds one stands alone.  Division and sqrtf are the correctly
+// rounded defaults.  The constants are formed on the host (fplx_optim_consts below); k0..k4 mean per kind:
+//   SGD       k0 momentum                                        Adadelta  k0 rho, k1 1 - rho, k2 eps
+//   Adagrad   lr = lr / (1 + (step - 1) lr_decay), k2 eps         Adamax    lr = lr / (1 - b1^step), k0 b1, k1 1 - b1, k2 eps, k3 b2
+//   ASGD      lr = eta, k0 = 1 - lambd eta, k3 mu                 RMSprop   k0 alpha, k1 1 - alpha, k2 eps, k3 momentum
+//   Rprop     k0 etaminus, k1 etaplus, k3 / k4 smallest / largest step size, first: step == 1 (prev = 0, step_size = lr)
+struct FplxOptimConst { float lr, wd, gscale, k0, k1, k2, k3, k4; int first; };
+__device__ __forceinline__ float fplx_optim_grad(float pi, float g, const FplxOptimConst& c) {
+  return fmaf(c.wd, pi, g * c.gscale);
+}
+template <bool MOM>
+__device__ __forceinline__ void fplx_sgd_elem(float& pi, float g, float& buf, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  if (MOM) {
+    buf = fmaf(c.k0, buf, gi);                     // the first buffer is the gradient: k0 * 0 + gi
+    pi = fmaf(-c.lr, buf, pi);
+  } else {
+    pi = fmaf(-c.lr, gi, pi);
+  }
+}
+__device__ __forceinline__ void fplx_adadelta_elem(float& pi, float g, float& sq, float& acc, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  sq = fmaf(c.k0, sq, (c.k1 * gi) * gi);
+  const float stdv = sqrtf(sq + c.k2);
+  const float ratio = sqrtf(acc + c.k2) / stdv;
+  const float delta = ratio * gi;
+  acc = fmaf(c.k0, acc, (c.k1 * delta) * delta);
+  pi = fmaf(-c.lr, delta, pi);
+}
+__device__ __forceinline__ void fplx_adagrad_elem(float& pi, float g, float& sum, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  sum = fmaf(gi, gi, sum);
+  const float stdv = sqrtf(sum) + c.k2;
+  pi = fmaf(-c.lr, gi / stdv, pi);
+}
+__device__ __forceinline__ void fplx_adamax_elem(float& pi, float g, float& mi, float& ui, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  mi = fmaf(c.k0, mi, c.k1 * gi);
+  const float decayed = c.k3 * ui;
+  ui = fmaxf(decayed, fabsf(gi) + c.k2);
+  pi = fmaf(-c.lr, mi / ui, pi);
+}
+__device__ __forceinline__ void fplx_asgd_elem(float& pi, float g, float& ax, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  const float decayed = pi * c.k0;                 // p *= 1 - lambd * eta
+  pi = fmaf(-c.lr, gi, decayed);                   // p -= eta * g
+  const float d = pi - ax;
+  ax = c.k3 == 1.f ? pi : fmaf(d, c.k3, ax);
+}
+template <bool MOM>
+__device__ __forceinline__ void fplx_rmsprop_elem(float& pi, float g, float& sq, float& buf, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  sq = fmaf(c.k0, sq, (c.k1 * gi) * gi);
+  const float avg = sqrtf(sq) + c.k2;
+  if (MOM) {
+    buf = fmaf(c.k3, buf, gi / avg);
+    pi = fmaf(-c.lr, buf, pi);
+  } else {
+    pi = fmaf(-c.lr, gi / avg, pi);
+  }
+}
+__device__ __forceinline__ void fplx_rprop_elem(float& pi, float g, float& prev, float& ss, const FplxOptimConst& c) {
+  float gi = g * c.gscale;                         // no weight decay (get_optimizer.py:34)
+  if (c.first) { prev = 0.f; ss = c.lr; }
+  const float s = gi * prev;                       // sign(g * prev) of the fp32 product
+  const float f = s > 0.f ? c.k1 : (s < 0.f ? c.k0 : 1.f);
+  const float scaled = ss * f;
+  ss = fminf(fmaxf(scaled, c.k3), c.k4);
+  if (s < 0.f) gi = 0.f;
+  const float sg = gi > 0.f ? 1.f : (gi < 0.f ? -1.f : 0.f);
+  pi = fmaf(-sg, ss, pi);
+  prev = gi;
+}
+// kind + number of state streams -> the element function; NS distinguishes SGD / RMSprop with and without a momentum buffer
+template <int KIND, int NS>
+__device__ __forceinline__ void fplx_optim_elem(float& pi, float g, float& s0, float& s1, const FplxOptimConst& c) {
+  if constexpr (KIND == FPLX_OPT_SGD) fplx_sgd_elem<NS == 1>(pi, g, s0, c);
+  else if constexpr (KIND == FPLX_OPT_ADADELTA) fplx_adadelta_elem(pi, g, s0, s1, c);
+  else if constexpr (KIND == FPLX_OPT_ADAGRAD) fplx_adagrad_elem(pi, g, s0, c);
+  else if constexpr (KIND == FPLX_OPT_ADAMAX) fplx_adamax_elem(pi, g, s0, s1, c);
+  else if constexpr (KIND == FPLX_OPT_ASGD) fplx_asgd_elem(pi, g, s0, c);
+  else if constexpr (KIND == FPLX_OPT_RMSPROP) fplx_rmsprop_elem<NS == 2>(pi, g, s0, s1, c);
+  else fplx_rprop_elem(pi, g, s0, s1, c);
+}
+// a kind / state-count pair as a compile-time constant: FPLX_OPTIM_DISPATCH(kind, ns, LAUNCH) expands LAUNCH(KIND, NS)
+#define FPLX_OPTIM_DISPATCH(kind, ns, X)                                       \
+  switch ((kind) * 4 + (ns)) {                                                 \
+    case FPLX_OPT_SGD * 4 + 0: X(FPLX_OPT_SGD, 0); break;                      \
+    case FPLX_OPT_SGD * 4 + 1: X(FPLX_OPT_SGD, 1); break;                      \
+    case FPLX_OPT_ADADELTA * 4 + 2: X(FPLX_OPT_ADADELTA, 2); break;            \
+    case FPLX_OPT_ADAGRAD * 4 + 1: X(FPLX_OPT_ADAGRAD, 1); break;              \
+    case FPLX_OPT_ADAMAX * 4 + 2: X(FPLX_OPT_ADAMAX, 2); break;                \
+    case FPLX_OPT_ASGD * 4 + 1: X(FPLX_OPT_ASGD, 1); break;                    \
+    case FPLX_OPT_RMSPROP * 4 + 1: X(FPLX_OPT_RMSPROP, 1); break;              \
+    case FPLX_OPT_RMSPROP * 4 + 2: X(FPLX_OPT_RMSPROP, 2); break;              \
+    default: X(FPLX_OPT_RPROP, 2); break;                                      \
+  }
+// host side of both entry points: checks kind / nhp / step / state pointers and forms the constants; the step-dependent
+// scalars in double, as fplx_adam_step forms lr / bc1.  *ns = number of state streams the launch touches.
+static inline int fplx_optim_consts(const char* who, int kind, const float* hp, int nhp, int step, float gscale, const void* s0,
+                                    const void* s1, FplxOptimConst* c, int* ns) {
+  static const int want[FPLX_OPT_COUNT] = {3, 4, 4, 5, 4, 5, 5};
+  FPLX_REQUIRE(kind >= 0 && kind < FPLX_OPT_COUNT, FPLX_E_BADSHAPE, "%s: unknown optimiser kind %d (0..%d)", who, kind,
+               FPLX_OPT_COUNT - 1);
+  FPLX_REQUIRE(hp, FPLX_E_NULL, "%s: null hyper-parameter array", who);
+  FPLX_REQUIRE(nhp == want[kind], FPLX_E_BADSHAPE, "%s: kind %d takes %d hyper-parameters, got %d", who, kind, want[kind], nhp);
+  FPLX_REQUIRE(step >= 1, FPLX_E_BADSHAPE, "%s: step=%d (1-based)", who, step);
+  *c = {hp[0], 0.f, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, step == 1};
+  int need = 2;
+  switch (kind) {
+    case FPLX_OPT_SGD:
+      c->k0 = hp[1]; c->wd = hp[2];
+      need = hp[1] != 0.f ? 1 : 0;
+      break;
+    case FPLX_OPT_ADADELTA:
+      c->k0 = hp[1]; c->k1 = (float)(1.0 - (double)hp[1]); c->k2 = hp[2]; c->wd = hp[3];
+      break;
+    case FPLX_OPT_ADAGRAD:
+      c->lr = (float)((double)hp[0] / (1.0 + (double)(step - 1) * (double)hp[1])); c->k2 = hp[2]; c->wd = hp[3];
+      need = 1;
+      break;
+    case FPLX_OPT_ADAMAX:
+      c->lr = (float)((double)hp[0] / (1.0 - pow((double)hp[1], step)));
+      c->k0 = hp[1]; c->k1 = (float)(1.0 - (double)hp[1]); c->k3 = hp[2]; c->k2 = hp[3]; c->wd = hp[4];
+      break;
+    case FPLX_OPT_ASGD:
+      c->k0 = (float)(1.0 - (double)hp[2] * (double)hp[0]); c->k3 = hp[1]; c->wd = hp[3];
+      need = 1;
+      break;
+    case FPLX_OPT_RMSPROP:
+      c->k0 = hp[1]; c->k1 = (float)(1.0 - (double)hp[1]); c->k2 = hp[2]; c->k3 = hp[3]; c->wd = hp[4];
+      need = hp[3] > 0.f ? 2 : 1;
+      break;
+    default:
+      c->k0 = hp[1]; c->k1 = hp[2]; c->k3 = hp[3]; c->k4 = hp[4];
+      break;
+  }
+  FPLX_REQUIRE((need < 1 || s0) && (need < 2 || s1), FPLX_E_NULL, "%s: kind %d needs %d state buffer(s) here", who, kind, need);
+  *ns = need;
+  return FPLX_OK;
 }
 // XCD-aware block order.  The dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs, each with its own
 // 4-MB L2, so blocks that share data (the cout blocks / tap splits of one voxel footprint, neighbouring footprints and

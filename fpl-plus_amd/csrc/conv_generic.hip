@@ -362,6 +362,27 @@ pack_conv_w27_tiled_multi(const PackTable t) {
   pack27_tile(t.w[e], t.wf[e], t.wb[e], t.cout[e], t.cin[e], (int)blockIdx.x - t.first[e], t.stamp[e], t.verify);
 }
 
+// second half of a fused update + pack block: the tile's updated weights are in LDS as bf16 (PK_CO rows of PK_ROW), out go both
+// packed layouts as 16-byte stores - exactly the second half of pack27_tile
+__device__ __forceinline__ void pack27_from_lds(const bf16_t* lds, bf16_t* wf, bf16_t* wb, int Cout, int Cin, int co0,
+                                                int ci0) {
+  union Pack8 { bf16_t h[8]; uint4 u; };
+  for (int i = threadIdx.x; i < 27 * PK_CO * (PK_CI / 8); i += 256) {          // wf: (tap, co, ci octet)
+    const int oct = i % (PK_CI / 8), co_l = (i / (PK_CI / 8)) % PK_CO, tap = i / ((PK_CI / 8) * PK_CO);
+    Pack8 pk;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pk.h[j] = lds[co_l * PK_ROW + (8 * oct + j) * 27 + tap];
+    *reinterpret_cast<uint4*>(wf + ((int64_t)tap * Cout + co0 + co_l) * Cin + ci0 + 8 * oct) = pk.u;
+  }
+  if (wb)
+    for (int i = threadIdx.x; i < 27 * PK_CI * (PK_CO / 8); i += 256) {        // wb: (tap, ci, co octet), taps flipped
+      const int half = i % (PK_CO / 8), ci_l = (i / (PK_CO / 8)) % PK_CI, tap = i / ((PK_CO / 8) * PK_CI);
+      Pack8 pk;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pk.h[j] = lds[(8 * half + j) * PK_ROW + ci_l * 27 + tap];
+      *reinterpret_cast<uint4*>(wb + ((int64_t)(26 - tap) * Cin + ci0 + ci_l) * Cout + co0 + 8 * half) = pk.u;
+    }
+}
 // Adam + weight pack in ONE launch (round 5): the weights change only in the optimiser step, and every forward opened with
 // pack_conv_w27_tiled_multi re-reading all 22 M master weights (48 us at the head of the step, where nothing overlaps it).
 // Blocks [0, tiles): a pack tile (16 co x 32 ci x 27 taps) of one 3x3x3 layer - the block applies Adam to ITS 13 824
@@ -426,24 +447,76 @@ adam_pack27_multi(const AdamPackTable t) {
     Act<bf16_t>::st(d, pv.x); Act<bf16_t>::st(d + 1, pv.y); Act<bf16_t>::st(d + 2, pv.z); Act<bf16_t>::st(d + 3, pv.w);
   }
   __syncthreads();
-  bf16_t* wf = t.wf[e];
-  bf16_t* wb = t.wb[e];
-  union Pack8 { bf16_t h[8]; uint4 u; };
-  for (int i = threadIdx.x; i < 27 * PK_CO * (PK_CI / 8); i += 256) {          // wf: (tap, co, ci octet)
-    const int oct = i % (PK_CI / 8), co_l = (i / (PK_CI / 8)) % PK_CO, tap = i / ((PK_CI / 8) * PK_CO);
-    Pack8 pk;
+  pack27_from_lds(lds, t.wf[e], t.wb[e], Cout, Cin, co0, ci0);
+}
+
+// The same launch for the seven other optimisers (fplx_optim_pack_step): adam_pack27_multi with the element function swapped -
+// the table's layer / gap geometry, the stamps and the pack half (pack27_from_lds) are Adam's; NS state streams are touched.
+struct OptimPackTable {
+  float *p, *s0, *s1;
+  const float* g;
+  FplxOptimConst c;
+  int64_t off[PK_MAX];
+  bf16_t* wf[PK_MAX];
+  bf16_t* wb[PK_MAX];
+  float* stamp[PK_MAX];
+  int cout[PK_MAX], cin[PK_MAX], first[PK_MAX + 1], n;
+  int64_t gstart[AP_MAXGAP], glen[AP_MAXGAP];
+  int gfirst[AP_MAXGAP + 1], ng;
+};
+template <int KIND, int NS>
+__global__ void __launch_bounds__(256)
+optim_pack27_multi(const OptimPackTable t) {
+  const int b = (int)blockIdx.x;
+  if (b >= t.first[t.n]) {             // ---- a gap block: the plain update on up to 1024 elements
+    const int gb = b - t.first[t.n];
+    int e = 0;
+    while (e + 1 < t.ng && gb >= t.gfirst[e + 1]) ++e;
+    const int64_t lo = (int64_t)(gb - t.gfirst[e]) * AP_GAPBLK, len = t.glen[e];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) pk.h[j] = lds[co_l * PK_ROW + (8 * oct + j) * 27 + tap];
-    *reinterpret_cast<uint4*>(wf + ((int64_t)tap * Cout + co0 + co_l) * Cin + ci0 + 8 * oct) = pk.u;
-  }
-  if (wb)
-    for (int i = threadIdx.x; i < 27 * PK_CI * (PK_CO / 8); i += 256) {        // wb: (tap, ci, co octet), taps flipped
-      const int half = i % (PK_CO / 8), ci_l = (i / (PK_CO / 8)) % PK_CI, tap = i / ((PK_CO / 8) * PK_CI);
-      Pack8 pk;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pk.h[j] = lds[(8 * half + j) * PK_ROW + ci_l * 27 + tap];
-      *reinterpret_cast<uint4*>(wb + ((int64_t)(26 - tap) * Cin + ci0 + ci_l) * Cout + co0 + 8 * half) = pk.u;
+    for (int k = 0; k < AP_GAPBLK / 256; ++k) {
+      const int64_t i = lo + threadIdx.x + 256 * k;
+      if (i < len) {
+        const int64_t x = t.gstart[e] + i;
+        float pi = t.p[x], a = 0.f, c = 0.f;
+        if (NS > 0) a = t.s0[x];
+        if (NS > 1) c = t.s1[x];
+        fplx_optim_elem<KIND, NS>(pi, t.g[x], a, c, t.c);
+        if (NS > 0) t.s0[x] = a;
+        if (NS > 1) t.s1[x] = c;
+        t.p[x] = pi;
+      }
     }
+    return;
+  }
+  int e = 0;
+  while (e + 1 < t.n && b >= t.first[e + 1]) ++e;
+  const int Cout = t.cout[e], Cin = t.cin[e], blk = b - t.first[e];
+  __shared__ bf16_t lds[PK_CO * PK_ROW];
+  const int ci_tiles = Cin / PK_CI;
+  const int co0 = (blk / ci_tiles) * PK_CO, ci0 = (blk % ci_tiles) * PK_CI;
+  constexpr int SEG4 = PK_CI * 27 / 4;
+  for (int i = threadIdx.x; i < PK_CO * SEG4; i += 256) {
+    const int co_l = i / SEG4, q = i % SEG4;
+    const int64_t x = t.off[e] + ((int64_t)(co0 + co_l) * Cin + ci0) * 27 + 4 * q;
+    float4 pv = *reinterpret_cast<const float4*>(t.p + x);
+    const float4 gv = *reinterpret_cast<const float4*>(t.g + x);
+    float4 av = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
+    if (NS > 0) av = *reinterpret_cast<const float4*>(t.s0 + x);
+    if (NS > 1) cv = *reinterpret_cast<const float4*>(t.s1 + x);
+    fplx_optim_elem<KIND, NS>(pv.x, gv.x, av.x, cv.x, t.c);
+    fplx_optim_elem<KIND, NS>(pv.y, gv.y, av.y, cv.y, t.c);
+    fplx_optim_elem<KIND, NS>(pv.z, gv.z, av.z, cv.z, t.c);
+    fplx_optim_elem<KIND, NS>(pv.w, gv.w, av.w, cv.w, t.c);
+    if (NS > 0) *reinterpret_cast<float4*>(t.s0 + x) = av;
+    if (NS > 1) *reinterpret_cast<float4*>(t.s1 + x) = cv;
+    *reinterpret_cast<float4*>(t.p + x) = pv;
+    if (t.stamp[e] && q % PK_STAMP_Q == 0) t.stamp[e][(int64_t)blk * PK_STAMP + co_l * 2 + q / PK_STAMP_Q] = pv.x;
+    bf16_t* d = lds + co_l * PK_ROW + 4 * q;
+    Act<bf16_t>::st(d, pv.x); Act<bf16_t>::st(d + 1, pv.y); Act<bf16_t>::st(d + 2, pv.z); Act<bf16_t>::st(d + 3, pv.w);
+  }
+  __syncthreads();
+  pack27_from_lds(lds, t.wf[e], t.wb[e], Cout, Cin, co0, ci0);
 }
 
 // the small packs of a step in ONE launch (round 5): stem, transposed convolutions, out_conv - seven launches of 3-6 us each with
@@ -688,18 +761,10 @@ int fplx_adam_pack_ok(int cout, int cin) {
   return fplx_knob(FPLX_K_PACK_TILED) != 0 && fplx_knob(FPLX_K_PACK_MULTI) != 0 && cin % PK_CI == 0 && cout % PK_CO == 0;
 }
 
-int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                        float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
-                        const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream) {
-  FPLX_REQUIRE(p && g && m && v && off && cout && cin && wf && wb, FPLX_E_NULL, "adam_pack_step: null pointer");
-  FPLX_REQUIRE(n > 0 && step >= 1 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "adam_pack_step: n=%lld step=%d layers=%d (1..%d)",
-               (long long)n, step, nl, PK_MAX);
-  FPLX_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               FPLX_E_BADSHAPE, "adam_pack_step: the flat buffers must be 16-byte aligned");
-  AdamPackTable t;
-  t.p = p; t.g = g; t.m = m; t.v = v;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  t.c = {(float)((double)lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, 1.f - beta1, 1.f - beta2};
+// layer / gap geometry of a fused update + pack launch (AdamPackTable and OptimPackTable carry the same fields)
+extern "C++" template <typename Table>
+static int fill_pack_table(const char* who, Table& t, int64_t n, int nl, const int64_t* off, const int* cout, const int* cin,
+                           void* const* wf, void* const* wb, float* const* stamp) {
   t.n = nl;
   t.first[0] = 0;
   t.ng = 0;
@@ -713,9 +778,9 @@ int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n,
   };
   for (int i = 0; i < nl; ++i) {
     const int64_t len = (int64_t)cout[i] * cin[i] * 27;
-    FPLX_REQUIRE(fplx_adam_pack_ok(cout[i], cin[i]) && wf[i], FPLX_E_BADSHAPE, "adam_pack_step: layer %d (%d x %d) not packable here (fplx_adam_pack_ok)", i, cout[i], cin[i]);
-    FPLX_REQUIRE(off[i] >= pos && off[i] % 4 == 0 && off[i] + len <= n, FPLX_E_BADSHAPE, "adam_pack_step: layer %d: offsets must ascend, be multiples of 4 and lie inside the segment", i);
-    FPLX_REQUIRE(((uintptr_t)wf[i] % 16) == 0 && ((uintptr_t)wb[i] % 16) == 0, FPLX_E_BADSHAPE, "adam_pack_step: packs must be 16-byte aligned");
+    FPLX_REQUIRE(fplx_adam_pack_ok(cout[i], cin[i]) && wf[i], FPLX_E_BADSHAPE, "%s: layer %d (%d x %d) not packable here (fplx_adam_pack_ok)", who, i, cout[i], cin[i]);
+    FPLX_REQUIRE(off[i] >= pos && off[i] % 4 == 0 && off[i] + len <= n, FPLX_E_BADSHAPE, "%s: layer %d: offsets must ascend, be multiples of 4 and lie inside the segment", who, i);
+    FPLX_REQUIRE(((uintptr_t)wf[i] % 16) == 0 && ((uintptr_t)wb[i] % 16) == 0, FPLX_E_BADSHAPE, "%s: packs must be 16-byte aligned", who);
     gap(pos, off[i]);
     t.off[i] = off[i]; t.cout[i] = cout[i]; t.cin[i] = cin[i]; t.wf[i] = (bf16_t*)wf[i]; t.wb[i] = (bf16_t*)wb[i];
     t.stamp[i] = stamp ? stamp[i] : nullptr;
@@ -723,8 +788,47 @@ int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n,
     pos = off[i] + len;
   }
   gap(pos, n);
+  return FPLX_OK;
+}
+
+int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
+                        const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream) {
+  FPLX_REQUIRE(p && g && m && v && off && cout && cin && wf && wb, FPLX_E_NULL, "adam_pack_step: null pointer");
+  FPLX_REQUIRE(n > 0 && step >= 1 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "adam_pack_step: n=%lld step=%d layers=%d (1..%d)",
+               (long long)n, step, nl, PK_MAX);
+  FPLX_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+               FPLX_E_BADSHAPE, "adam_pack_step: the flat buffers must be 16-byte aligned");
+  AdamPackTable t;
+  t.p = p; t.g = g; t.m = m; t.v = v;
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  t.c = {(float)((double)lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, 1.f - beta1, 1.f - beta2};
+  const int rc = fill_pack_table("adam_pack_step", t, n, nl, off, cout, cin, wf, wb, stamp);
+  if (rc != FPLX_OK) return rc;
   adam_pack27_multi<<<t.first[t.n] + t.gfirst[t.ng], 256, 0, (hipStream_t)stream>>>(t);
   return fplx_check_launch("adam_pack_step");
+}
+
+int fplx_optim_pack_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                         float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin, void* const* wf,
+                         void* const* wb, float* const* stamp, fplx_stream_t stream) {
+  FPLX_REQUIRE(p && g && off && cout && cin && wf && wb, FPLX_E_NULL, "optim_pack_step: null pointer");
+  FPLX_REQUIRE(n > 0 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "optim_pack_step: n=%lld layers=%d (1..%d)", (long long)n, nl, PK_MAX);
+  OptimPackTable t;
+  int ns = 0;
+  int rc = fplx_optim_consts("optim_pack_step", kind, hp, nhp, step, grad_scale, s0, s1, &t.c, &ns);
+  if (rc != FPLX_OK) return rc;
+  FPLX_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && (ns < 1 || ((uintptr_t)s0 % 16) == 0) &&
+               (ns < 2 || ((uintptr_t)s1 % 16) == 0), FPLX_E_BADSHAPE, "optim_pack_step: the flat buffers must be 16-byte aligned");
+  t.p = p; t.g = g; t.s0 = s0; t.s1 = s1;
+  rc = fill_pack_table("optim_pack_step", t, n, nl, off, cout, cin, wf, wb, stamp);
+  if (rc != FPLX_OK) return rc;
+  const int grid = t.first[t.n] + t.gfirst[t.ng];
+  hipStream_t st = (hipStream_t)stream;
+#define FPLX_OPTIM_LAUNCH(K, S) optim_pack27_multi<K, S><<<grid, 256, 0, st>>>(t)
+  FPLX_OPTIM_DISPATCH(kind, ns, FPLX_OPTIM_LAUNCH)
+#undef FPLX_OPTIM_LAUNCH
+  return fplx_check_launch("optim_pack_step");
 }
 
 int fplx_pack_deconv_weight(const float* w, void* wf, void* wb, int cin, int cout, int dt, fplx_stream_t stream) {

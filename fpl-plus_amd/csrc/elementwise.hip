@@ -925,6 +925,45 @@ adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m
 }
 
 
+// The seven other optimisers of get_optimizer (get_optimizer.py:13-34), one kernel per kind and state count: HBM-bound, so the
+// aligned body moves one 16-byte vector per lane and stream (p, g and the NS state streams the kind has - nothing else is
+// touched), and a scalar head and tail take whatever is left of ANY n at ANY 4-byte-aligned base: the BN segments of the flat
+// buffer do not start on 16 bytes.  head: elements in front of p's first 16-byte boundary; VEC only if g and the state streams
+// reach theirs at the same element (the host checks), else every element goes through the scalar loop.
+template <int KIND, int NS, bool VEC>
+__global__ void __launch_bounds__(EW_THREADS)
+optim_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1, int64_t n,
+        int64_t head, const FplxOptimConst c) {
+  const int64_t tid = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * EW_THREADS;
+  const int64_t nv = VEC ? (n - head) / 4 : 0, body_end = head + 4 * nv;
+  for (int64_t i = tid; i < nv; i += stride) {
+    const int64_t x = head + 4 * i;
+    float4 pv = *reinterpret_cast<const float4*>(p + x);
+    const float4 gv = *reinterpret_cast<const float4*>(g + x);
+    float4 av = {0.f, 0.f, 0.f, 0.f}, bv = {0.f, 0.f, 0.f, 0.f};
+    if (NS > 0) av = *reinterpret_cast<const float4*>(s0 + x);
+    if (NS > 1) bv = *reinterpret_cast<const float4*>(s1 + x);
+    fplx_optim_elem<KIND, NS>(pv.x, gv.x, av.x, bv.x, c);
+    fplx_optim_elem<KIND, NS>(pv.y, gv.y, av.y, bv.y, c);
+    fplx_optim_elem<KIND, NS>(pv.z, gv.z, av.z, bv.z, c);
+    fplx_optim_elem<KIND, NS>(pv.w, gv.w, av.w, bv.w, c);
+    if (NS > 0) *reinterpret_cast<float4*>(s0 + x) = av;
+    if (NS > 1) *reinterpret_cast<float4*>(s1 + x) = bv;
+    *reinterpret_cast<float4*>(p + x) = pv;
+  }
+  const int64_t rest = head + (n - body_end);                          // VEC: at most 3 + 3 elements; else all n
+  for (int64_t j = tid; j < rest; j += stride) {
+    const int64_t x = j < head ? j : body_end + (j - head);
+    float pi = p[x], a = 0.f, b = 0.f;
+    if (NS > 0) a = s0[x];
+    if (NS > 1) b = s1[x];
+    fplx_optim_elem<KIND, NS>(pi, g[x], a, b, c);
+    if (NS > 0) s0[x] = a;
+    if (NS > 1) s1[x] = b;
+    p[x] = pi;
+  }
+}
+
 // per-channel sum / sum of squares of an NDHWC tensor: part [rows][2][C] (standalone DSBN layer)
 template <typename T>
 __global__ void __launch_bounds__(EW_THREADS)
@@ -1236,6 +1275,33 @@ int fplx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
   adam_k<<<ew_grid(n), EW_THREADS, 0, (hipStream_t)stream>>>(p, g, m, v, n, (float)((double)lr / bc1), beta1, beta2, eps,
                                                             weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale);
   return fplx_check_launch("adam_step");
+}
+
+int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                    float grad_scale, fplx_stream_t stream) {
+  FPLX_REQUIRE(p && g, FPLX_E_NULL, "optim_step: null pointer");
+  FPLX_REQUIRE(n > 0, FPLX_E_BADSHAPE, "optim_step: n=%lld", (long long)n);
+  FplxOptimConst c;
+  int ns = 0;
+  const int rc = fplx_optim_consts("optim_step", kind, hp, nhp, step, grad_scale, s0, s1, &c, &ns);
+  if (rc != FPLX_OK) return rc;
+  FPLX_REQUIRE((uintptr_t)p % 4 == 0 && (uintptr_t)g % 4 == 0 && (ns < 1 || (uintptr_t)s0 % 4 == 0) && (ns < 2 || (uintptr_t)s1 % 4 == 0),
+               FPLX_E_BADSHAPE, "optim_step: the buffers must be 4-byte aligned");
+  const uintptr_t ph = (uintptr_t)p % 16;
+  int64_t head = (int64_t)((16 - ph) % 16) / 4;
+  if (head > n) head = n;
+  const bool vec = (uintptr_t)g % 16 == ph && (ns < 1 || (uintptr_t)s0 % 16 == ph) && (ns < 2 || (uintptr_t)s1 % 16 == ph);
+  if (!vec) head = 0;
+  const int grid = ew_grid(vec ? (n - head) / 4 + 6 : n);
+  hipStream_t st = (hipStream_t)stream;
+#define FPLX_OPTIM_LAUNCH(K, S)                                                                       \
+  do {                                                                                                \
+    if (vec) optim_k<K, S, true><<<grid, EW_THREADS, 0, st>>>(p, g, s0, s1, n, head, c);              \
+    else optim_k<K, S, false><<<grid, EW_THREADS, 0, st>>>(p, g, s0, s1, n, head, c);                 \
+  } while (0)
+  FPLX_OPTIM_DISPATCH(kind, ns, FPLX_OPTIM_LAUNCH)
+#undef FPLX_OPTIM_LAUNCH
+  return fplx_check_launch("optim_step");
 }
 
 }  // extern "C"

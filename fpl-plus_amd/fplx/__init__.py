@@ -15,7 +15,8 @@ from .loss import (SegLossDict, DiceLoss, CrossEntropyLoss, DiceLoss_weight, Com
                    GeneralizedCELoss, MAELoss, MSELoss, SLSRLoss)
 from .infer import Inferer                                         # noqa: E402
 from .agent import SegmentationAgent, SegNetDict                   # noqa: E402
-from .optim import FusedAdam, get_optimizer, get_lr_scheduler      # noqa: E402
+from .optim import (FusedOptimizer, FusedAdam, FusedSGD, FusedAdadelta, FusedAdagrad, FusedAdamax, FusedASGD,  # noqa: E402
+                    FusedRMSprop, FusedRprop, get_optimizer, get_lr_scheduler)
 from .train import TrainStep                                       # noqa: E402
 from .config import parse_config, synchronize_config               # noqa: E402
 from .dataset import NiftyDataset                                  # noqa: E402
@@ -24,7 +25,8 @@ from . import filter, ops, ddp, transform, nifti, evaluation, postprocess       
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
-           "SegmentationAgent", "FusedAdam", "get_optimizer", "get_lr_scheduler", "TrainStep",
+           "SegmentationAgent", "FusedOptimizer", "FusedAdam", "FusedSGD", "FusedAdadelta", "FusedAdagrad", "FusedAdamax", "FusedASGD",
+           "FusedRMSprop", "FusedRprop", "get_optimizer", "get_lr_scheduler", "TrainStep",
            "parse_config", "synchronize_config", "filter", "ops", "ddp", "transform", "nifti", "evaluation", "NiftyDataset",
            "postprocess", "SegLossDictAll", "FocalDiceLoss", "NoiseRobustDiceLoss", "ExpLogLoss", "GeneralizedCELoss", "MAELoss",
            "MSELoss", "SLSRLoss", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]

@@ -11,7 +11,8 @@ translates both ways:
   * reference_model_state_dict(net): all 484 keys - the dead twins are re-emitted verbatim if they came in with a loaded
     checkpoint, else filled with neutral values of the right shape - so the reference's strict load_state_dict accepts it;
   * optimizer_to_reference / optimizer_from_reference: torch.optim.Adam's {'state': {index: {step, exp_avg, exp_avg_sq}},
-    'param_groups': [...]} with indices in the reference's parameter order.  torch gives a parameter state only once it has
+    'param_groups': [...]} with indices in the reference's parameter order - and the same for the seven other optimisers
+    (fplx/optim.py), each with its own state keys.  torch gives a parameter state only once it has
     seen a gradient and counts steps per parameter; here steps are counted per flat segment (shared | BN of domain d), which
     is the same thing because a domain's BN parameters always step together (dsbn.py:56).
 """
@@ -105,24 +106,63 @@ def reference_model_state_dict(net):
     return out
 
 
+def _torch_group_defaults(opt):
+    """param-group keys of the installed torch.optim.<TORCH> that the fused class does not carry (foreach, maximize, ...)"""
+    if opt.TORCH == "Adam":
+        return (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False),
+                ("differentiable", False), ("fused", None), ("decoupled_weight_decay", False))
+    probe = getattr(torch.optim, opt.TORCH)([torch.zeros(1)], lr=1e-3)
+    return tuple(probe.defaults.items())
+
+
+def optimizer_name_of(sd):
+    """which torch optimiser wrote the state_dict `sd` (by the keys only it has), or None"""
+    g = sd["param_groups"][0] if sd.get("param_groups") else {}
+    keys = set()
+    for st in sd.get("state", {}).values():
+        keys |= set(st)
+    for name, group_key, state_key in (("Adadelta", "rho", "acc_delta"), ("Adagrad", "lr_decay", "sum"), ("ASGD", "lambd", "ax"),
+                                       ("Rprop", "etas", "step_size"), ("RMSprop", "alpha", "square_avg"),
+                                       ("Adamax", None, "exp_inf"), ("Adam", "amsgrad", "exp_avg_sq"),
+                                       ("SGD", "nesterov", None)):
+        if (group_key is not None and group_key in g) or (state_key is not None and state_key in keys):
+            return name
+    if "betas" in g:
+        return "Adamax"
+    if "momentum" in g or "momentum_buffer" in keys:
+        return "SGD"
+    return None
+
+
 def optimizer_to_reference(opt):
-    """FusedAdam -> torch.optim.Adam state_dict over the reference's 268-entry parameter list"""
+    """fused optimiser -> torch.optim.<TORCH> state_dict over the reference's 268-entry parameter list: per parameter a `step`
+    tensor (all but SGD), the class's state tensors under torch's names, ASGD's eta and mu; nothing for the parameters of a
+    segment that never stepped (torch creates state at a parameter's first gradient; Adagrad alone creates it at construction,
+    so there it is step 0 and a zero sum) and nothing at all for SGD without momentum"""
     net = opt.net
     names = reference_param_names(net.num_domains)
     index = {k: i for i, k in enumerate(names)}
+    active = opt._active_state()
+    scalars = opt._segment_scalars()
     state = {}
     for si, (start, end) in enumerate(opt.seg_ranges):
-        if opt.seg_steps[si] == 0:
+        if opt.seg_steps[si] == 0 and opt.TORCH != "Adagrad":
             continue                                           # never stepped: torch holds no state for these
+        if not opt.HAS_STEP and not active:
+            continue
         for k in net._order:
             o, n, shp = net._layout[k]
             if start <= o < end:
-                state[index[k]] = {"step": torch.tensor(float(opt.seg_steps[si])),
-                                   "exp_avg": opt.exp_avg[o:o + n].view(shp).clone(),
-                                   "exp_avg_sq": opt.exp_avg_sq[o:o + n].view(shp).clone()}
+                st = {}
+                if opt.HAS_STEP:
+                    st["step"] = torch.tensor(float(opt.seg_steps[si]))
+                for sk, vals in scalars.items():               # seg_eta / seg_mu -> eta / mu
+                    st[sk[4:]] = torch.tensor(float(vals[si]))
+                for name in active:
+                    st[name] = opt._buffer(name)[o:o + n].view(shp).clone()
+                state[index[k]] = st
     g = {k: v for k, v in opt.param_groups[0].items() if k != "params"}
-    for k, v in (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False),
-                 ("differentiable", False), ("fused", None), ("decoupled_weight_decay", False)):
+    for k, v in _torch_group_defaults(opt):
         g.setdefault(k, v)
     g["params"] = list(range(len(names)))
     return {"state": dict(sorted(state.items())), "param_groups": [g]}
@@ -131,6 +171,10 @@ def optimizer_to_reference(opt):
 def optimizer_from_reference(opt, sd):
     net = opt.net
     names = reference_param_names(net.num_domains)
+    wrote = optimizer_name_of(sd)
+    if wrote is not None and wrote != opt.TORCH:
+        raise ValueError("fplx: this is a state of torch.optim.{0:}, the optimiser is {1:} (torch.optim.{2:})".format(
+            wrote, type(opt).__name__, opt.TORCH))
     if len(sd["param_groups"]) != 1 or len(sd["param_groups"][0]["params"]) != len(names):
         raise ValueError("fplx: optimizer state has {0:} parameters, the reference network has {1:}".format(
             sum(len(g["params"]) for g in sd["param_groups"]), len(names)))
@@ -139,8 +183,13 @@ def optimizer_from_reference(opt, sd):
     stray = [k for k in by_name if k not in net._layout]
     if stray:
         raise ValueError("fplx: optimizer state for parameters this build does not train: {0:}".format(stray[:4]))
-    opt.exp_avg.zero_()
-    opt.exp_avg_sq.zero_()
+    for k, v in sd["param_groups"][0].items():                 # first: which state streams exist depends on the momentum
+        if k != "params":
+            opt.param_groups[0][k] = v
+    active = opt._active_state()
+    scalars = opt._segment_scalars()
+    for name in active:
+        opt._buffer(name).zero_()
     steps = []
     for si, (start, end) in enumerate(opt.seg_ranges):
         seen = set()
@@ -149,18 +198,20 @@ def optimizer_from_reference(opt, sd):
             if not (start <= o < end):
                 continue
             st = by_name.get(k)
-            seen.add(None if st is None else int(round(float(st["step"]))))
+            if st is not None and not all(name in st for name in active):
+                raise ValueError("fplx: optimizer state of {0:} lacks {1:} (torch.optim.{2:})".format(
+                    k, [name for name in active if name not in st], opt.TORCH))
+            seen.add(None if st is None else (int(round(float(st["step"]))) if opt.HAS_STEP else 1))
             if st is not None:
-                opt.exp_avg[o:o + n].copy_(st["exp_avg"].reshape(-1))
-                opt.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+                for name in active:
+                    opt._buffer(name)[o:o + n].copy_(st[name].reshape(-1))
+                for sk, vals in scalars.items():
+                    vals[si] = float(st[sk[4:]])
         if len(seen) != 1:
-            raise ValueError("fplx: parameters of one segment carry different Adam step counts {0:}".format(seen))
+            raise ValueError("fplx: parameters of one segment carry different {0:} step counts {1:}".format(opt.TORCH, seen))
         s = seen.pop()
         steps.append(0 if s is None else s)
     opt.seg_steps = steps
-    for k, v in sd["param_groups"][0].items():
-        if k != "params":
-            opt.param_groups[0][k] = v
 
 
 # ---- files (agent_seg.py:701-704, 786-830; agent_abstract.py:136-153)

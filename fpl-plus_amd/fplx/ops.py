@@ -552,6 +552,34 @@ def adam_pack_step(p, g, m, v, lr, step, weight_decay, grad_scale, betas, eps, l
          vp(*[ptr(l[3]) for l in layers]), vp(*[ptr(l[4]) or None for l in layers]), st, stream())
 
 
+OPTIM_KINDS = ("SGD", "Adadelta", "Adagrad", "Adamax", "ASGD", "RMSprop", "Rprop")      # FPLX_OPT_* in include/fplx.h
+
+
+def _optim_args(kind, p, g, s0, s1, hp, step, grad_scale):
+    import ctypes
+    k = OPTIM_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    hp = [float(x) for x in hp]
+    return (k, ptr(p), ptr(g), ptr(s0) or None, ptr(s1) or None, p.numel(), (ctypes.c_float * len(hp))(*hp), len(hp),
+            int(step), grad_scale)
+
+
+def optim_step(kind, p, g, s0, s1, hp, step, grad_scale=1.0):
+    """fplx_optim_step: one step of `kind` (a name of OPTIM_KINDS or its FPLX_OPT_* number) over the flat fp32 segment p.
+    s0 / s1: the kind's state streams or None; hp: the kind's hyper-parameters in the order include/fplx.h documents."""
+    call("fplx_optim_step", *(_optim_args(kind, p, g, s0, s1, hp, step, grad_scale) + (stream(),)))
+
+
+def optim_pack_step(kind, p, g, s0, s1, hp, step, grad_scale, layers):
+    """fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside p in one launch; layers as in adam_pack_step"""
+    import ctypes
+    n = len(layers)
+    vp, ip, lp = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_int64 * n
+    st = vp(*[(ptr(l[5]) or None) if len(l) > 5 else None for l in layers])
+    call("fplx_optim_pack_step", *(_optim_args(kind, p, g, s0, s1, hp, step, grad_scale) + (
+        n, lp(*[int(l[0]) for l in layers]), ip(*[int(l[1]) for l in layers]), ip(*[int(l[2]) for l in layers]),
+        vp(*[ptr(l[3]) for l in layers]), vp(*[ptr(l[4]) or None for l in layers]), st, stream())))
+
+
 def mc_filter(logits_tcv, thr=0.01, want_hards=True, want_maps=False):
     """logits_tcv: fp32 [T, C, ...volume...] on the GPU -> dict (device tensors, no sync)"""
     require_gpu(logits_tcv)

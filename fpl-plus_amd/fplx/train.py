@@ -18,7 +18,7 @@ class TrainStep(object):
     def __init__(self, net, loss_terms=(1.0, 0.0, 0.0, 0.0), softmax=True, lr=1e-4, weight_decay=1e-5,
                  milestones=(), gamma=0.5, group=None, bucket_elems=1 << 21, optimizer=None, loss_ext=None):
         """loss_ext: terms of the second loss family, as AbstractSegLoss.ext_spec() gives them (None: the first family's pass);
-        optimizer: an existing fplx.FusedAdam over `net` (SegmentationAgent routes its training loops through this class and
+        optimizer: an existing fused optimiser (fplx.FusedAdam, FusedSGD, ...: fplx.optim.FUSED_CLASSES) over `net` (SegmentationAgent routes its training loops through this class and
         keeps ITS optimiser - state, param_groups, the torch lr scheduler stepping it); its learning rate is then whatever the
         param_group says at the time of the step, `lr` / `milestones` / `gamma` are not used."""
         net._ensure_flat()

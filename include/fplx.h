@@ -453,6 +453,37 @@ int fplx_adam_pack_ok(int cout, int cin);
 int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
                         const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream);
+/* The seven other optimisers get_optimizer can run (net_run_dsbn/get_optimizer.py:13-34; it passes lr, momentum and
+ * weight_decay only, everything else is torch's default), one launch over a flat fp32 segment, with the arithmetic of torch's
+ * _single_tensor_* functions.  p, g, s0, s1: any 4-byte-aligned base, any n > 0.  hp: HOST array of nhp floats; s0 / s1: the
+ * kind's state streams, read and written (a stream the kind does not have is never touched and may be NULL):
+ *   kind                hp                                               s0               s1
+ *   FPLX_OPT_SGD        lr, momentum, weight_decay                       momentum_buffer  -               get_optimizer.py:13-15
+ *                       (momentum == 0: no state at all; the first buffer is the gradient, i.e. momentum * 0 + g)
+ *   FPLX_OPT_ADADELTA   lr, rho, eps, weight_decay                       square_avg       acc_delta       get_optimizer.py:20-21
+ *   FPLX_OPT_ADAGRAD    lr, lr_decay, eps, weight_decay                  sum              -               get_optimizer.py:22-23
+ *   FPLX_OPT_ADAMAX     lr, beta1, beta2, eps, weight_decay              exp_avg          exp_inf         get_optimizer.py:24-25
+ *   FPLX_OPT_ASGD       eta, mu, lambd, weight_decay                     ax               -               get_optimizer.py:26-27
+ *                       (eta and mu are the caller's per-segment scalars: torch forms the next step's pair after the update,
+ *                        eta = lr / (1 + lambd lr step)^alpha, mu = 1 / max(1, step - t0); they start as lr and 1)
+ *   FPLX_OPT_RMSPROP    lr, alpha, eps, momentum, weight_decay           square_avg       momentum_buffer get_optimizer.py:30-32
+ *                       (s1 only if momentum > 0; not centred)
+ *   FPLX_OPT_RPROP      lr, etaminus, etaplus, step_min, step_max        prev             step_size       get_optimizer.py:33-34
+ *                       (no weight decay; at step == 1 the incoming s0 / s1 are ignored: prev = 0, step_size = lr)
+ * step (1-based) enters Adagrad's lr / (1 + (step - 1) lr_decay) and Adamax's lr / (1 - beta1^step), formed in double on the
+ * host like fplx_adam_step's lr / bc1; grad_scale multiplies g first (for Rprop that keeps sign and zero, which is all it reads).
+ * FPLX_E_BADSHAPE: unknown kind, n <= 0, step < 1, wrong nhp; FPLX_E_NULL: a missing pointer the kind needs. */
+enum { FPLX_OPT_SGD = 0, FPLX_OPT_ADADELTA, FPLX_OPT_ADAGRAD, FPLX_OPT_ADAMAX, FPLX_OPT_ASGD, FPLX_OPT_RMSPROP, FPLX_OPT_RPROP,
+       FPLX_OPT_COUNT };
+int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                    float grad_scale, fplx_stream_t stream);
+/* fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside the segment in one launch: fplx_adam_pack_step with the
+ * element function swapped (same table, same layer rules - fplx_adam_pack_ok -, same stamps); p, g and the kind's state
+ * streams must be 16-byte aligned.  Same parameters, state and packs as fplx_optim_step followed by
+ * fplx_pack_conv_weights_batched, bit for bit. */
+int fplx_optim_pack_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                         float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin, void* const* wf,
+                         void* const* wb, float* const* stamp, fplx_stream_t stream);
 
 /* ------------------------------------------------------------------ pseudo-label filter
  * FPL branch of SegmentationAgent.infer (net_run_dsbn/agent_seg.py:911-931) for one volume:
