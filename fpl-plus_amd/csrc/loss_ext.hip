@@ -3,6 +3,10 @@
 // 4C + 4 new ones, one finalize thread turns the totals into values and a coefficient table, one backward pass writes dlogits for
 // any mixture of the eleven terms.  Which terms run is a bit mask in the kernel arguments: wave-uniform branches, so the powf /
 // logf work of a term that was not asked for is never issued.  Layouts: include/fplx.h, "segmentation loss, second family".
+// Shared with loss_filter.hip through loss_common.h: dispatch, checks, the sums region, seg_loss_sums_k, the first family's
+// finalize, and of the backward voxel loop seg_loss_base_grad and seg_loss_ent_grad.  The forward voxel loop and the rest of
+// the backward one are two copies on purpose: a shared device function there stays only if every instantiation that uses it keeps its
+// text or its counts of fused multiply-adds, multiplies and adds (-ffp-contract=fast fuses after inlining).
 #include "loss_common.h"
 
 namespace {
@@ -82,6 +86,7 @@ seg_loss_ext_fwd_k(const float* __restrict__ logits, const float* __restrict__ l
     }
     softmax_argmax<C>(l, p, do_softmax != 0);
     float ce = 0.f, ent = 0.f;
+    // the first 6C + 3 sums are seg_loss_fwd_k's lines (loss_filter.hip): two copies under the rule above
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       acc[6 * c + 0] += y[c] * w;
@@ -94,7 +99,7 @@ seg_loss_ext_fwd_k(const float* __restrict__ logits, const float* __restrict__ l
       acc[K0 + 4 * c + 0] += p[c];
       acc[K0 + 4 * c + 1] += y[c] * p[c];
     }
-    // the CE numerator and the entropy sum are part of every pass, as in seg_loss_fwd_k (out[2], out[3] report them)
+    // the CE numerator and the entropy sum are part of every pass: seg_loss_fwd_k's lines, its twin under the rule above
     float q[MAXC];
     if (do_softmax) {
 #pragma unroll
@@ -154,70 +159,19 @@ seg_loss_ext_fwd_k(const float* __restrict__ logits, const float* __restrict__ l
   }
 }
 
-// one block: the partial rows in double to per-sample sums [N][K] and their total over the local samples [K] (seg_loss_sums_k
-// with K as an argument)
-__global__ void seg_loss_ext_sums_k(const float* __restrict__ part, int rows, int N, int K, double* __restrict__ sums,
-                                    double* __restrict__ totals) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int i = wv; i < N * K; i += nw) {
-    const int n = i / K, k = i % K;
-    double s = 0.0;
-    for (int r = lane; r < rows; r += 64) s += (double)part[((int64_t)n * rows + r) * K + k];
-    s = wave_sum_d(s);
-    if (lane == 0) sums[i] = s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    double t = 0.0;
-    for (int n = 0; n < N; ++n) t += sums[n * K + threadIdx.x];      // fixed order
-    totals[threadIdx.x] = t;
-  }
-}
-
-// one thread: values and the backward coefficient table.  The first family's part repeats seg_loss_coef_k expression for
-// expression.  coef: [N][C][2] (A, B of the pixel-weighted Dice terms), cce, cent; then per class (Au, Bu: the unweighted
+// one thread: values and the backward coefficient table.  The first family's part is seg_loss_base_finalize (loss_common.h),
+// as in seg_loss_coef_k.  coef: [N][C][2] (A, B of the pixel-weighted Dice terms), cce, cent; then per class (Au, Bu: the unweighted
 // Dice-type terms as Au y + Bu, cnr, cel); then cgce, 2 cmse, cmae, cslsr.
 __global__ void seg_loss_ext_coef_k(const double* __restrict__ sums, const double* __restrict__ tot, int N, int NG, int C,
                                     double V, int has_pw, const float* __restrict__ image_weight, ExtCfg cf,
                                     float* __restrict__ out, float* __restrict__ coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const int K = 10 * C + 7, K0 = 6 * C + 3, S0 = 10 * C + 3;
-  const float w_dice = cf.f[CF_DICE], w_ce = cf.f[CF_CE], w_img = cf.f[CF_IMG], w_ent = cf.f[CF_ENT];
-  double Ld = 0.0, Limg = 0.0, Lce = 0.0, Lent = 0.0;
-  for (int i = 0; i < N * C * 2; ++i) coef[i] = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const double* t = tot + 6 * c;
-    const double den = t[0] + t[1] + 1e-5, num = 2.0 * t[2] + 1e-5;
-    Ld += num / den;
-    out[4 + c] = (float)((2.0 * t[5] + 1e-5) / (t[3] + t[4] + 1e-5));
-    for (int n = 0; n < N; ++n) {
-      coef[(n * C + c) * 2 + 0] += (float)(w_dice * (-2.0 / (C * den)));
-      coef[(n * C + c) * 2 + 1] += (float)(w_dice * (num / (C * den * den)));
-    }
-  }
-  Ld = 1.0 - Ld / C;
-  if (w_img != 0.f && image_weight) {
-    for (int n = 0; n < N; ++n) {
-      double dn = 0.0;
-      const double f = (double)image_weight[n] / NG;
-      for (int c = 0; c < C; ++c) {
-        const double* s = sums + n * K + 6 * c;
-        const double den = s[0] + s[1] + 1e-5, num = 2.0 * s[2] + 1e-5;
-        dn += num / den;
-        coef[(n * C + c) * 2 + 0] += (float)(w_img * f * (-2.0 / (C * den)));
-        coef[(n * C + c) * 2 + 1] += (float)(w_img * f * (num / (C * den * den)));
-      }
-      Limg += f * (1.0 - dn / C);
-    }
-  }
   const double M = NG * V;
-  const double cenum = tot[6 * C + 0], wsum = tot[6 * C + 1], ent = tot[6 * C + 2];
-  const double ce_norm = has_pw ? 1.0 / (wsum + 1e-5) : 1.0 / M;          // ce.py:39-43
-  Lce = cenum * ce_norm;
-  Lent = ent / M;                                                         // agent_seg.py:352-353
   float* ce2 = coef + N * C * 2;
-  ce2[0] = (float)(w_ce * ce_norm);
-  ce2[1] = (float)(w_ent / M);
+  double total = seg_loss_base_finalize(sums, tot, N, NG, C, K, V, has_pw, image_weight, cf.f[CF_DICE], cf.f[CF_CE], cf.f[CF_IMG],
+                                        cf.f[CF_ENT], out, coef);
+  const double wsum = tot[6 * C + 1];
   // ---- second family
   const double w_focal = cf.f[CF_FOCAL], w_nr = cf.f[CF_NR], w_el = cf.f[CF_EXPLOG], w_gce = cf.f[CF_GCE], w_mae = cf.f[CF_MAE],
                w_mse = cf.f[CF_MSE], w_slsr = cf.f[CF_SLSR];
@@ -266,10 +220,6 @@ __global__ void seg_loss_ext_coef_k(const double* __restrict__ sums, const doubl
   cs[1] = (float)(2.0 * w_mse / (M * C));
   cs[2] = (float)(w_mae / (M * C));
   cs[3] = (float)(w_slsr / M);
-  double total = w_dice * Ld + w_img * Limg + w_ce * Lce + w_ent * Lent;
-  out[1] = (float)(w_dice * Ld + w_img * Limg);
-  out[2] = (float)Lce;
-  out[3] = (float)Lent;
   float* oe = out + 4 + C;
   oe[0] = oe[1] = oe[2] = oe[3] = oe[4] = oe[5] = oe[6] = 0.f;
   if (w_focal != 0.0) { total += w_focal * Lf; oe[0] = (float)Lf; }
@@ -306,7 +256,6 @@ seg_loss_ext_bwd_k(const float* __restrict__ logits, const float* __restrict__ l
   const float cce = ce2[0], cent = ce2[1], gs = *gscale;
   const float cgce = cc[4 * C + 0], cmse2 = cc[4 * C + 1], cmae = cc[4 * C + 2], cslsr = cc[4 * C + 3];
   const float gnr1 = a.gnr - 1.0f, gel1 = a.gel - 1.0f, q1 = a.q - 1.0f;
-  const float inv_ln2 = 1.4426950408889634f;
   for (int64_t v = (int64_t)blockIdx.x * LT + threadIdx.x; v < V; v += (int64_t)gridDim.x * LT) {
     float l[MAXC], p[MAXC], g[MAXC];
 #pragma unroll
@@ -315,7 +264,8 @@ seg_loss_ext_bwd_k(const float* __restrict__ logits, const float* __restrict__ l
     const float wg = (fl & T_GCE_PW) ? w : 1.f;
     const bool masked = wp && w > 0.f;
     softmax_argmax<C>(l, p, do_softmax != 0);
-    // without loss_softmax every term but the entropy one sends its gradient to the outputs directly
+    // without loss_softmax every term but the entropy one sends its gradient to the outputs directly (the Jacobian below is
+    // seg_loss_bwd_k's, its twin under the rule above)
     const bool ent_own = use_ent && !do_softmax;
     float q[MAXC], ge[MAXC], dote = 0.f;
     if (ent_own) softmax_argmax<C>(l, q, true);
@@ -323,12 +273,9 @@ seg_loss_ext_bwd_k(const float* __restrict__ logits, const float* __restrict__ l
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float y = lb[(int64_t)c * V + v];
-      float gc = 0.f;
-      if (use_dice) gc += w * fmaf(A[c], y, B[c]);
-      if (use_ce) gc -= cce * w * y * 0.999f / (p[c] * 0.999f + 5e-4f);
-      if (use_ent && do_softmax) gc -= cent * (log2f(p[c] + 1e-10f) + p[c] * inv_ln2 / (p[c] + 1e-10f));
+      float gc = seg_loss_base_grad(use_dice, use_ce, use_ent && do_softmax, w, A[c], B[c], cce, cent, y, p[c]);
       if (ent_own) {
-        ge[c] = -cent * (log2f(q[c] + 1e-10f) + q[c] * inv_ln2 / (q[c] + 1e-10f));
+        ge[c] = seg_loss_ent_grad(cent, q[c]);
         dote = fmaf(ge[c], q[c], dote);
       }
       if (use_u) gc += fmaf(Au[c], y, Bu[c]);
@@ -356,33 +303,14 @@ seg_loss_ext_bwd_k(const float* __restrict__ logits, const float* __restrict__ l
   }
 }
 
-inline int grid1(int64_t v, int cap) {
-  int64_t g = (v + LT - 1) / LT;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 int ext_check(const char* what, int n, int c, int64_t v, const float* cfg) {
-  FPLX_REQUIRE(n > 0 && n <= 64 && c >= 1 && c <= MAXC && v > 0, FPLX_E_BADSHAPE, "%s: n=%d (<=64) c=%d (<=%d) v=%lld", what, n,
-               c, MAXC, (long long)v);
+  const int rc = loss_shape_check(what, n, c, v);
+  if (rc != FPLX_OK) return rc;
   FPLX_REQUIRE(cfg, FPLX_E_NULL, "%s: null cfg", what);
   return FPLX_OK;
 }
 
 }  // namespace
-
-#define DISPATCH_C(C, KERNEL, ...)                 \
-  switch (C) {                                     \
-    case 1: KERNEL<1> __VA_ARGS__; break;          \
-    case 2: KERNEL<2> __VA_ARGS__; break;          \
-    case 3: KERNEL<3> __VA_ARGS__; break;          \
-    case 4: KERNEL<4> __VA_ARGS__; break;          \
-    case 5: KERNEL<5> __VA_ARGS__; break;          \
-    case 6: KERNEL<6> __VA_ARGS__; break;          \
-    case 7: KERNEL<7> __VA_ARGS__; break;          \
-    default: KERNEL<8> __VA_ARGS__; break;         \
-  }
 
 extern "C" {
 
@@ -397,7 +325,7 @@ int fplx_seg_loss_ext_sums(const float* logits, const float* label, const float*
   const int rows = loss_rows(v);
   dim3 grid(rows, n);
   DISPATCH_C(c, seg_loss_ext_fwd_k, <<<grid, LT, 0, st>>>(logits, label, pixel_weight, v, softmax, a, part));
-  seg_loss_ext_sums_k<<<1, 1024, 0, st>>>(part, rows, n, FPLX_LOSS_EXT_K(c), sums, totals);
+  seg_loss_sums_k<<<1, 1024, 0, st>>>(part, rows, n, FPLX_LOSS_EXT_K(c), sums, totals);
   return fplx_check_launch("seg_loss_ext_sums");
 }
 
@@ -427,13 +355,10 @@ int fplx_seg_loss_ext_fwd(const float* logits, const float* label, const float* 
   FPLX_REQUIRE(logits && label && part && out && coef, FPLX_E_NULL, "seg_loss_ext_fwd: null pointer");
   FPLX_REQUIRE(cfg[CF_IMG] == 0.f || (image_weight && pixel_weight), FPLX_E_NULL,
                "seg_loss_ext_fwd: image-weighted Dice needs image_weight and pixel_weight");
-  // the per-sample sums live in the spare rows of the caller's `part` buffer (fplx_loss_rows), as in fplx_seg_loss_fwd
-  const int rows = loss_rows(v), K = FPLX_LOSS_EXT_K(c);
-  double* sums = reinterpret_cast<double*>(part + (((size_t)n * rows * K + 1) / 2) * 2);
-  double* totals = sums + (size_t)n * K;
-  rc = fplx_seg_loss_ext_sums(logits, label, pixel_weight, n, c, v, cfg, softmax, part, sums, totals, stream);
+  const LossSums s = loss_sums_region(part, n, loss_rows(v), FPLX_LOSS_EXT_K(c));
+  rc = fplx_seg_loss_ext_sums(logits, label, pixel_weight, n, c, v, cfg, softmax, part, s.sums, s.totals, stream);
   if (rc != FPLX_OK) return rc;
-  return fplx_seg_loss_ext_from_sums(sums, totals, image_weight, n, n, c, v, pixel_weight != nullptr, cfg, out, coef, stream);
+  return fplx_seg_loss_ext_from_sums(s.sums, s.totals, image_weight, n, n, c, v, pixel_weight != nullptr, cfg, out, coef, stream);
 }
 
 int fplx_seg_loss_ext_bwd(const float* logits, const float* label, const float* pixel_weight, const float* coef,

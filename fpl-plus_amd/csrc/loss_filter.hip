@@ -32,7 +32,8 @@ seg_loss_fwd_k(const float* __restrict__ logits, const float* __restrict__ label
         if (l[c] > best) { best = l[c]; am = c; }
     }
     softmax_argmax<C>(l, p, do_softmax != 0);
-    // the entropy regulariser takes softmax(outputs) whatever loss_softmax says (agent_seg.py:353): q = p with do_softmax
+    // the entropy regulariser takes softmax(outputs) whatever loss_softmax says (agent_seg.py:353): q = p with do_softmax.
+    // seg_loss_ext_fwd_k (loss_ext.hip) repeats this loop: two copies under the rule stated there.
     float q[MAXC];
     if (do_softmax) {
 #pragma unroll
@@ -72,75 +73,13 @@ seg_loss_fwd_k(const float* __restrict__ logits, const float* __restrict__ label
   }
 }
 
-// one block: reduce the partial rows (double) to per-sample sums [N][K] and their total over the local samples [K]
-__global__ void seg_loss_sums_k(const float* __restrict__ part, int rows, int N, int C, double* __restrict__ sums,
-                                double* __restrict__ totals) {
-  const int K = 6 * C + 3;
-  // one wave per (n, k) sum: lanes stride over rows
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int i = wv; i < N * K; i += nw) {
-    const int n = i / K, k = i % K;
-    double s = 0.0;
-    for (int r = lane; r < rows; r += 64) s += (double)part[((int64_t)n * rows + r) * K + k];
-    s = wave_sum_d(s);
-    if (lane == 0) sums[i] = s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    double t = 0.0;
-    for (int n = 0; n < N; ++n) t += sums[n * K + threadIdx.x];      // fixed order
-    totals[threadIdx.x] = t;
-  }
-}
-
-// one thread: the loss terms and the backward coefficient table from the per-sample sums of the LOCAL samples and the
-// totals over the WHOLE batch (= the local totals in one process; all-reduced over the ranks under data parallelism, where
-// the reference's nn.DataParallel gathers the logits and evaluates ONE loss over the full batch, agent_seg.py:692-698)
+// one thread: seg_loss_base_finalize (loss_common.h) is the whole of this family's finalize
 __global__ void seg_loss_coef_k(const double* __restrict__ sums, const double* __restrict__ tot, int N, int NG, int C,
                                 double V, int has_pw, const float* __restrict__ image_weight, float w_dice, float w_ce,
                                 float w_img, float w_ent, float* __restrict__ out, float* __restrict__ coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const int K = 6 * C + 3;
-  double Ld = 0.0, Limg = 0.0, Lce = 0.0, Lent = 0.0;
-  for (int i = 0; i < N * C * 2; ++i) coef[i] = 0.f;
-  // global Dice over all voxels of the batch (dice.py:20-57)
-  for (int c = 0; c < C; ++c) {
-    const double* t = tot + 6 * c;
-    const double den = t[0] + t[1] + 1e-5, num = 2.0 * t[2] + 1e-5;
-    Ld += num / den;
-    out[4 + c] = (float)((2.0 * t[5] + 1e-5) / (t[3] + t[4] + 1e-5));
-    for (int n = 0; n < N; ++n) {
-      coef[(n * C + c) * 2 + 0] += (float)(w_dice * (-2.0 / (C * den)));
-      coef[(n * C + c) * 2 + 1] += (float)(w_dice * (num / (C * den * den)));
-    }
-  }
-  Ld = 1.0 - Ld / C;
-  // per-sample Dice times image weight, mean over the batch (dice.py:106-128): this rank's samples only; the terms of the
-  // other ranks' samples are theirs (the value is completed by the caller's all-reduce when it wants the number)
-  if (w_img != 0.f && image_weight) {
-    for (int n = 0; n < N; ++n) {
-      double dn = 0.0;
-      const double f = (double)image_weight[n] / NG;
-      for (int c = 0; c < C; ++c) {
-        const double* s = sums + n * K + 6 * c;
-        const double den = s[0] + s[1] + 1e-5, num = 2.0 * s[2] + 1e-5;
-        dn += num / den;
-        coef[(n * C + c) * 2 + 0] += (float)(w_img * f * (-2.0 / (C * den)));
-        coef[(n * C + c) * 2 + 1] += (float)(w_img * f * (num / (C * den * den)));
-      }
-      Limg += f * (1.0 - dn / C);
-    }
-  }
-  const double cenum = tot[6 * C + 0], wsum = tot[6 * C + 1], ent = tot[6 * C + 2];
-  const double ce_norm = has_pw ? 1.0 / (wsum + 1e-5) : 1.0 / (NG * V);   // ce.py:39-43
-  Lce = cenum * ce_norm;
-  Lent = ent / (NG * V);                                                  // agent_seg.py:352-353
-  coef[N * C * 2 + 0] = (float)(w_ce * ce_norm);
-  coef[N * C * 2 + 1] = (float)(w_ent / (NG * V));
-  out[0] = (float)(w_dice * Ld + w_img * Limg + w_ce * Lce + w_ent * Lent);
-  out[1] = (float)(w_dice * Ld + w_img * Limg);
-  out[2] = (float)Lce;
-  out[3] = (float)Lent;
+  out[0] = (float)seg_loss_base_finalize(sums, tot, N, NG, C, 6 * C + 3, V, has_pw, image_weight, w_dice, w_ce, w_img, w_ent, out,
+                                         coef);
 }
 
 template <int C>
@@ -157,7 +96,6 @@ seg_loss_bwd_k(const float* __restrict__ logits, const float* __restrict__ label
 #pragma unroll
   for (int c = 0; c < C; ++c) { A[c] = coef[(n * C + c) * 2]; B[c] = coef[(n * C + c) * 2 + 1]; }
   const float cce = coef[N * C * 2], cent = coef[N * C * 2 + 1], gs = *gscale;
-  const float inv_ln2 = 1.4426950408889634f;
   for (int64_t v = (int64_t)blockIdx.x * LT + threadIdx.x; v < V; v += (int64_t)gridDim.x * LT) {
     float l[MAXC], p[MAXC], g[MAXC];
 #pragma unroll
@@ -165,6 +103,7 @@ seg_loss_bwd_k(const float* __restrict__ logits, const float* __restrict__ label
     const float w = wp ? wp[v] : 1.f;
     softmax_argmax<C>(l, p, do_softmax != 0);
     // without loss_softmax the Dice / CE gradients go to the outputs directly, the entropy term's still through ITS softmax
+    // (seg_loss_ext_bwd_k in loss_ext.hip is this loop's twin; what the two share passes the rule stated there)
     const bool ent_own = use_ent && !do_softmax;
     float q[MAXC], ge[MAXC], dote = 0.f;
     if (ent_own) softmax_argmax<C>(l, q, true);
@@ -172,12 +111,9 @@ seg_loss_bwd_k(const float* __restrict__ logits, const float* __restrict__ label
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float y = lb[(int64_t)c * V + v];
-      float gc = 0.f;
-      if (use_dice) gc += w * fmaf(A[c], y, B[c]);
-      if (use_ce) gc -= cce * w * y * 0.999f / (p[c] * 0.999f + 5e-4f);
-      if (use_ent && do_softmax) gc -= cent * (log2f(p[c] + 1e-10f) + p[c] * inv_ln2 / (p[c] + 1e-10f));
+      float gc = seg_loss_base_grad(use_dice, use_ce, use_ent && do_softmax, w, A[c], B[c], cce, cent, y, p[c]);
       if (ent_own) {
-        ge[c] = -cent * (log2f(q[c] + 1e-10f) + q[c] * inv_ln2 / (q[c] + 1e-10f));
+        ge[c] = seg_loss_ent_grad(cent, q[c]);
         dote = fmaf(ge[c], q[c], dote);
       }
       g[c] = gc;
@@ -404,40 +340,16 @@ pixel_weight_k(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int
   }
 }
 
-inline int grid1(int64_t v, int cap) {
-  int64_t g = (v + LT - 1) / LT;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
-
-#define DISPATCH_C(C, KERNEL, ...)                 \
-  switch (C) {                                     \
-    case 1: KERNEL<1> __VA_ARGS__; break;          \
-    case 2: KERNEL<2> __VA_ARGS__; break;          \
-    case 3: KERNEL<3> __VA_ARGS__; break;          \
-    case 4: KERNEL<4> __VA_ARGS__; break;          \
-    case 5: KERNEL<5> __VA_ARGS__; break;          \
-    case 6: KERNEL<6> __VA_ARGS__; break;          \
-    case 7: KERNEL<7> __VA_ARGS__; break;          \
-    default: KERNEL<8> __VA_ARGS__; break;         \
-  }
 
 extern "C" {
 
-// rows to ALLOCATE per sample: the partial rows the kernels use plus 5 spare ones - behind the N x rows x K partials of a call
-// the spare N x 5 x K floats hold the per-sample sums and the batch totals as doubles ((N + 1) x K doubles = 2 (N + 1) K floats)
-// plus the one float the 8-byte alignment of that region may cost (K is odd): 2 (N + 1) K + 1 <= 5 N K for every N >= 1.
-// (With 4 spare rows N = 1 and an odd rows x K overran the buffer by one float: ADVICE r02.)
-int fplx_loss_rows(int64_t voxels_per_sample) { return loss_rows(voxels_per_sample) + 5; }
+// rows to ALLOCATE per sample: the partial rows the kernels use plus the spare ones of loss_sums_region (loss_common.h)
+int fplx_loss_rows(int64_t voxels_per_sample) { return loss_rows(voxels_per_sample) + LOSS_SPARE_ROWS; }
 
 static int seg_loss_check(const char* what, const float* logits, const float* label, int n, int c, int64_t v) {
   FPLX_REQUIRE(logits && label, FPLX_E_NULL, "%s: null pointer", what);
-  FPLX_REQUIRE(n > 0 && n <= 64 && c >= 1 && c <= MAXC && v > 0, FPLX_E_BADSHAPE, "%s: n=%d (<=64) c=%d (<=%d) v=%lld", what, n,
-               c, MAXC, (long long)v);
-  return FPLX_OK;
+  return loss_shape_check(what, n, c, v);
 }
 
 int fplx_seg_loss_sums(const float* logits, const float* label, const float* pixel_weight, int n, int c, int64_t v,
@@ -449,7 +361,7 @@ int fplx_seg_loss_sums(const float* logits, const float* label, const float* pix
   const int rows = loss_rows(v);
   dim3 grid(rows, n);
   DISPATCH_C(c, seg_loss_fwd_k, <<<grid, LT, 0, st>>>(logits, label, pixel_weight, v, softmax, part));
-  seg_loss_sums_k<<<1, 1024, 0, st>>>(part, rows, n, c, sums, totals);
+  seg_loss_sums_k<<<1, 1024, 0, st>>>(part, rows, n, 6 * c + 3, sums, totals);
   return fplx_check_launch("seg_loss_sums");
 }
 
@@ -471,15 +383,12 @@ int fplx_seg_loss_fwd(const float* logits, const float* label, const float* pixe
   FPLX_REQUIRE(part && out && coef, FPLX_E_NULL, "seg_loss_fwd: null pointer");
   FPLX_REQUIRE(w_dice_img == 0.f || (image_weight && pixel_weight), FPLX_E_NULL,
                "seg_loss_fwd: image-weighted Dice needs image_weight and pixel_weight");
-  // the per-sample sums live in the spare rows of the caller's `part` buffer (fplx_loss_rows)
-  const int rows = loss_rows(v), K = 6 * c + 3;
   int rc = seg_loss_check("seg_loss_fwd", logits, label, n, c, v);
   if (rc != FPLX_OK) return rc;
-  double* sums = reinterpret_cast<double*>(part + (((size_t)n * rows * K + 1) / 2) * 2);
-  double* totals = sums + (size_t)n * K;
-  rc = fplx_seg_loss_sums(logits, label, pixel_weight, n, c, v, softmax, part, sums, totals, stream);
+  const LossSums s = loss_sums_region(part, n, loss_rows(v), 6 * c + 3);
+  rc = fplx_seg_loss_sums(logits, label, pixel_weight, n, c, v, softmax, part, s.sums, s.totals, stream);
   if (rc != FPLX_OK) return rc;
-  return fplx_seg_loss_from_sums(sums, totals, image_weight, n, n, c, v, pixel_weight != nullptr, w_dice, w_ce, w_dice_img,
+  return fplx_seg_loss_from_sums(s.sums, s.totals, image_weight, n, n, c, v, pixel_weight != nullptr, w_dice, w_ce, w_dice_img,
                                  w_entropy, out, coef, stream);
 }
 

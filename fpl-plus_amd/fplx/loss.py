@@ -17,35 +17,20 @@ from . import ops
 
 
 class _FusedSegLoss(torch.autograd.Function):
+    """one ops.LossPass (either family) as an autograd node"""
+
     @staticmethod
-    def forward(ctx, logits, label, pw, iw, weights, softmax, holder):
-        ops.require_gpu(logits, label, pw, iw)
-        if logits.dim() != 5:
-            raise ValueError("{0:}D tensor not supported".format(logits.dim()))        # loss/seg/util.py:46-47
-        if logits.shape != label.shape:
-            raise ValueError("fplx loss: prediction {0:} and ground_truth {1:} differ in shape".format(
-                tuple(logits.shape), tuple(label.shape)))
-        logits = logits.float().contiguous()
-        label = label.float().contiguous()
+    def forward(ctx, logits, label, pw, iw, lp, holder):
+        logits, label, pw, iw = prepare_inputs(lp, logits, label, pw, iw)
         n, c = logits.shape[0], logits.shape[1]
-        v = logits[0, 0].numel()
-        if pw is not None:
-            pw = pw.float().contiguous()
-            if pw.numel() != n * v:
-                raise ValueError("fplx loss: pixel_weight must be [N,1,D,H,W]")
-        if iw is not None:
-            iw = iw.float().contiguous()
+        k, nout, ncoef = lp.sizes(n, c)
         dev = logits.device
-        part = torch.empty((n, ops.loss_rows(v), ops.loss_k(c)), dtype=torch.float32, device=dev)
-        out = torch.empty(4 + c, dtype=torch.float32, device=dev)
-        coef = torch.empty(n * c * 2 + 2, dtype=torch.float32, device=dev)
-        group = getattr(holder, "dist_group", None) if holder is not None else None
-        if holder is not None and getattr(holder, "dist_sync", False):
-            ops.seg_loss_fwd_dist(logits, label, pw, iw, weights, softmax, part, out, coef, group)
-        else:
-            ops.seg_loss_fwd(logits, label, pw, iw, weights, softmax, part, out, coef)
+        part = torch.empty((n, ops.loss_rows(logits[0, 0].numel()), k), dtype=torch.float32, device=dev)
+        out = torch.empty(nout, dtype=torch.float32, device=dev)
+        coef = torch.empty(ncoef, dtype=torch.float32, device=dev)
+        lp.forward(logits, label, pw, iw, part, out, coef, getattr(holder, "dist_group", None), getattr(holder, "dist_sync", False))
         ctx.save_for_backward(logits, label, pw, coef)
-        ctx.weights, ctx.softmax = weights, softmax
+        ctx.lp = lp
         if holder is not None:
             holder.last_out = out
         return out[0]
@@ -54,53 +39,8 @@ class _FusedSegLoss(torch.autograd.Function):
     def backward(ctx, g):
         logits, label, pw, coef = ctx.saved_tensors
         dl = torch.empty_like(logits)
-        ops.seg_loss_bwd(logits, label, pw, coef, g.float().contiguous(), ctx.weights, ctx.softmax, dl)
-        return dl, None, None, None, None, None, None
-
-
-class _FusedSegLossExt(torch.autograd.Function):
-    """_FusedSegLoss for a loss with terms of the second family: the fplx_seg_loss_ext_* pass evaluates all eleven"""
-
-    @staticmethod
-    def forward(ctx, logits, label, pw, iw, weights, spec, softmax, holder):
-        ops.require_gpu(logits, label, pw, iw)
-        if logits.dim() != 5:
-            raise ValueError("{0:}D tensor not supported".format(logits.dim()))        # loss/seg/util.py:46-47
-        if logits.shape != label.shape:
-            raise ValueError("fplx loss: prediction {0:} and ground_truth {1:} differ in shape".format(
-                tuple(logits.shape), tuple(label.shape)))
-        logits = logits.float().contiguous()
-        label = label.float().contiguous()
-        n, c = logits.shape[0], logits.shape[1]
-        v = logits[0, 0].numel()
-        if pw is not None:
-            pw = pw.float().contiguous()
-            if pw.numel() != n * v:
-                raise ValueError("fplx loss: pixel_weight must be [N,1,D,H,W]")
-        if iw is not None:
-            iw = iw.float().contiguous()
-        dev = logits.device
-        cfg = ops.loss_ext_cfg(weights, spec, c)
-        part = torch.empty((n, ops.loss_rows(v), ops.loss_ext_k(c)), dtype=torch.float32, device=dev)
-        out = torch.empty(ops.loss_ext_nout(c), dtype=torch.float32, device=dev)
-        coef = torch.empty(ops.loss_ext_ncoef(n, c), dtype=torch.float32, device=dev)
-        group = getattr(holder, "dist_group", None) if holder is not None else None
-        if holder is not None and getattr(holder, "dist_sync", False):
-            ops.seg_loss_ext_fwd_dist(logits, label, pw, iw, cfg, softmax, part, out, coef, group)
-        else:
-            ops.seg_loss_ext_fwd(logits, label, pw, iw, cfg, softmax, part, out, coef)
-        ctx.save_for_backward(logits, label, pw, coef)
-        ctx.cfg, ctx.softmax = cfg, softmax
-        if holder is not None:
-            holder.last_out = out
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, label, pw, coef = ctx.saved_tensors
-        dl = torch.empty_like(logits)
-        ops.seg_loss_ext_bwd(logits, label, pw, coef, g.float().contiguous(), ctx.cfg, ctx.softmax, dl)
-        return dl, None, None, None, None, None, None, None
+        ctx.lp.backward(logits, label, pw, coef, g.float().contiguous(), dl)
+        return dl, None, None, None, None, None
 
 
 def ext_spec(ext, ext_params):
@@ -118,6 +58,29 @@ def check_ext_inputs(spec, pw):
     """what the reference raises before it computes (ce.py:85-88)"""
     if spec is not None and spec[0][ops.LOSS_EXT_TERMS.index("gce")] != 0.0 and spec[1][6] and pw is None:
         raise ValueError("Pixel weight is enabled but not defined")
+
+
+def prepare_inputs(lp, logits, label, pw, iw):
+    """the checks every route into the pass `lp` (ops.LossPass) makes, and fp32 contiguous tensors -> (logits, label, pw, iw)"""
+    if lp.terms[2] != 0.0 and (pw is None or iw is None):
+        raise KeyError('pixel_weight')                                   # dice.py:109-110 index the dict
+    if lp.terms[2] == 0.0:
+        iw = None
+    check_ext_inputs(lp.ext, pw)
+    ops.require_gpu(logits, label, pw, iw)
+    if logits.dim() != 5:
+        raise ValueError("{0:}D tensor not supported".format(logits.dim()))        # loss/seg/util.py:46-47
+    if logits.shape != label.shape:
+        raise ValueError("fplx loss: prediction {0:} and ground_truth {1:} differ in shape".format(
+            tuple(logits.shape), tuple(label.shape)))
+    logits, label = logits.float().contiguous(), label.float().contiguous()
+    if pw is not None:
+        pw = pw.float().contiguous()
+        if pw.numel() != logits.numel() // logits.shape[1]:
+            raise ValueError("fplx loss: pixel_weight must be [N,1,D,H,W]")
+    if iw is not None:
+        iw = iw.float().contiguous()
+    return logits, label, pw, iw
 
 
 class AbstractSegLoss(nn.Module):
@@ -141,19 +104,9 @@ class AbstractSegLoss(nn.Module):
         predict = loss_input_dict['prediction']
         if isinstance(predict, (list, tuple)):
             predict = predict[0]                                             # dice.py:26-27
-        pw = loss_input_dict.get('pixel_weight', None)
-        iw = loss_input_dict.get('image_weight', None)
-        if terms[2] != 0.0 and (pw is None or iw is None):
-            raise KeyError('pixel_weight')                                   # dice.py:109-110 index the dict
-        if terms[2] == 0.0:
-            iw = None
-        spec = self.ext_spec()
-        if spec is None:
-            return _FusedSegLoss.apply(predict, loss_input_dict['ground_truth'], pw, iw, tuple(float(t) for t in terms),
-                                       bool(self.softmax), self)
-        check_ext_inputs(spec, pw)
-        return _FusedSegLossExt.apply(predict, loss_input_dict['ground_truth'], pw, iw, tuple(float(t) for t in terms), spec,
-                                      bool(self.softmax), self)
+        lp = ops.LossPass(terms, self.ext_spec(), self.softmax)
+        return _FusedSegLoss.apply(predict, loss_input_dict['ground_truth'], loss_input_dict.get('pixel_weight', None),
+                                   loss_input_dict.get('image_weight', None), lp, self)
 
     def ext_spec(self):
         return ext_spec(self.ext, self.ext_params)

@@ -427,34 +427,48 @@ def loss_k(c):
     return 6 * c + 3
 
 
+def _ncv(logits):
+    return logits.shape[0], logits.shape[1], logits[0, 0].numel()
+
+
 def seg_loss_fwd(logits, label, pw, iw, weights, softmax, part, out, coef):
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
+    n, c, v = _ncv(logits)
     call("fplx_seg_loss_fwd", ptr(logits), ptr(label), ptr(pw), ptr(iw), n, c, v, weights[0], weights[1], weights[2],
          weights[3], 1 if softmax else 0, ptr(part), ptr(out), ptr(coef), stream())
 
 
-def seg_loss_fwd_dist(logits, label, pw, iw, weights, softmax, part, out, coef, group):
-    """seg_loss_fwd under data parallelism: the sums over the local samples are all-reduced over `group` between the
-    reduction and the evaluation, so loss, metric and backward coefficients are those of the FULL batch (what the
-    reference's nn.DataParallel computes on its gathered logits, agent_seg.py:692-698).  All ranks must hold the same
-    number of samples."""
+def _seg_loss_sums(logits, label, pw, weights, softmax, part, sums, totals):
+    n, c, v = _ncv(logits)                                   # the sums do not depend on the weights
+    call("fplx_seg_loss_sums", ptr(logits), ptr(label), ptr(pw), n, c, v, 1 if softmax else 0, ptr(part), ptr(sums), ptr(totals),
+         stream())
+
+
+def _seg_loss_from_sums(sums, totals, iw, n, n_global, c, v, has_pw, weights, out, coef):
+    call("fplx_seg_loss_from_sums", ptr(sums), ptr(totals), ptr(iw), n, n_global, c, v, 1 if has_pw else 0, weights[0], weights[1],
+         weights[2], weights[3], ptr(out), ptr(coef), stream())
+
+
+def _fwd_dist(sums_fn, from_sums_fn, k, logits, label, pw, iw, how, softmax, part, out, coef, group):
+    """a forward under data parallelism: the sums over the local samples are all-reduced over `group` between the reduction
+    and the evaluation, so loss, metric and backward coefficients are those of the FULL batch (what the reference's
+    nn.DataParallel computes on its gathered logits, agent_seg.py:692-698; every sum of either family is additive over the
+    ranks).  All ranks must hold the same number of samples.  how: the family's weights or cfg."""
     import torch.distributed as dist
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
-    k = loss_k(c)
+    n, c, v = _ncv(logits)
     sums = torch.empty((n + 1, k), dtype=torch.float64, device=logits.device)
-    call("fplx_seg_loss_sums", ptr(logits), ptr(label), ptr(pw), n, c, v, 1 if softmax else 0, ptr(part), ptr(sums[:n]),
-         ptr(sums[n]), stream())
+    sums_fn(logits, label, pw, how, softmax, part, sums[:n], sums[n])
     dist.all_reduce(sums[n], op=dist.ReduceOp.SUM, group=group)
-    world = dist.get_world_size(group)
-    call("fplx_seg_loss_from_sums", ptr(sums[:n]), ptr(sums[n]), ptr(iw), n, n * world, c, v, 0 if pw is None else 1,
-         weights[0], weights[1], weights[2], weights[3], ptr(out), ptr(coef), stream())
+    from_sums_fn(sums[:n], sums[n], iw, n, n * dist.get_world_size(group), c, v, pw is not None, how, out, coef)
+
+
+def seg_loss_fwd_dist(logits, label, pw, iw, weights, softmax, part, out, coef, group):
+    """seg_loss_fwd over the full batch of all ranks (_fwd_dist)"""
+    _fwd_dist(_seg_loss_sums, _seg_loss_from_sums, loss_k(logits.shape[1]), logits, label, pw, iw, weights, softmax, part, out, coef,
+              group)
 
 
 def seg_loss_bwd(logits, label, pw, coef, gscale, weights, softmax, dlogits):
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
+    n, c, v = _ncv(logits)
     call("fplx_seg_loss_bwd", ptr(logits), ptr(label), ptr(pw), ptr(coef), ptr(gscale), n, c, v, weights[0],
          weights[1], weights[2], weights[3], 1 if softmax else 0, ptr(dlogits), stream())
 
@@ -494,15 +508,13 @@ def loss_ext_cfg(terms, ext, c):
 
 
 def seg_loss_ext_fwd(logits, label, pw, iw, cfg, softmax, part, out, coef):
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
+    n, c, v = _ncv(logits)
     call("fplx_seg_loss_ext_fwd", ptr(logits), ptr(label), ptr(pw), ptr(iw), n, c, v, cfg, 1 if softmax else 0, ptr(part),
          ptr(out), ptr(coef), stream())
 
 
 def seg_loss_ext_sums(logits, label, pw, cfg, softmax, part, sums, totals):
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
+    n, c, v = _ncv(logits)
     call("fplx_seg_loss_ext_sums", ptr(logits), ptr(label), ptr(pw), n, c, v, cfg, 1 if softmax else 0, ptr(part), ptr(sums),
          ptr(totals), stream())
 
@@ -513,22 +525,53 @@ def seg_loss_ext_from_sums(sums, totals, iw, n, n_global, c, v, has_pw, cfg, out
 
 
 def seg_loss_ext_fwd_dist(logits, label, pw, iw, cfg, softmax, part, out, coef, group):
-    """seg_loss_ext_fwd under data parallelism, as seg_loss_fwd_dist: every new sum is additive over the ranks"""
-    import torch.distributed as dist
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
-    sums = torch.empty((n + 1, loss_ext_k(c)), dtype=torch.float64, device=logits.device)
-    seg_loss_ext_sums(logits, label, pw, cfg, softmax, part, sums[:n], sums[n])
-    dist.all_reduce(sums[n], op=dist.ReduceOp.SUM, group=group)
-    world = dist.get_world_size(group)
-    seg_loss_ext_from_sums(sums[:n], sums[n], iw, n, n * world, c, v, pw is not None, cfg, out, coef)
+    """seg_loss_ext_fwd over the full batch of all ranks (_fwd_dist)"""
+    _fwd_dist(seg_loss_ext_sums, seg_loss_ext_from_sums, loss_ext_k(logits.shape[1]), logits, label, pw, iw, cfg, softmax, part, out,
+              coef, group)
 
 
 def seg_loss_ext_bwd(logits, label, pw, coef, gscale, cfg, softmax, dlogits):
-    n, c = logits.shape[0], logits.shape[1]
-    v = logits[0, 0].numel()
+    n, c, v = _ncv(logits)
     call("fplx_seg_loss_ext_bwd", ptr(logits), ptr(label), ptr(pw), ptr(coef), ptr(gscale), n, c, v, cfg, 1 if softmax else 0,
          ptr(dlogits), stream())
+
+
+class LossPass(object):
+    """One fused loss pass: the first family's (ext None: terms = the weights of Dice, CE, image-weighted Dice, entropy) or, with
+    ext = (weights, parameters) of the second family's terms (AbstractSegLoss.ext_spec()), the pass that evaluates all eleven.
+    The only place the two families' buffer sizes and entry points are chosen between; the entry points are looked up on this
+    module at the time of the call."""
+
+    def __init__(self, terms, ext, softmax):
+        self.terms, self.ext, self.softmax = tuple(float(t) for t in terms), ext, bool(softmax)
+        self._cfg = {}
+
+    def sizes(self, n, c):
+        """partial-row width k, floats of `out`, floats of `coef`"""
+        if self.ext is None:
+            return loss_k(c), 4 + c, n * c * 2 + 2
+        return loss_ext_k(c), loss_ext_nout(c), loss_ext_ncoef(n, c)
+
+    def _args(self, c):
+        """what the family's entry points take behind the tensors: the four weights, or cfg (built once per class count)"""
+        if self.ext is None:
+            return self.terms
+        if c not in self._cfg:
+            self._cfg[c] = loss_ext_cfg(self.terms, self.ext, c)
+        return self._cfg[c]
+
+    def forward(self, logits, label, pw, iw, part, out, coef, group=None, dist=False):
+        """dist: over the full batch of the ranks of `group` (None: the default group)"""
+        how = self._args(logits.shape[1])
+        if dist:
+            (seg_loss_fwd_dist if self.ext is None else seg_loss_ext_fwd_dist)(logits, label, pw, iw, how, self.softmax, part, out,
+                                                                               coef, group)
+        else:
+            (seg_loss_fwd if self.ext is None else seg_loss_ext_fwd)(logits, label, pw, iw, how, self.softmax, part, out, coef)
+
+    def backward(self, logits, label, pw, coef, gscale, dlogits):
+        (seg_loss_bwd if self.ext is None else seg_loss_ext_bwd)(logits, label, pw, coef, gscale, self._args(logits.shape[1]),
+                                                                 self.softmax, dlogits)
 
 
 def adam_step(p, g, m, v, lr, step, weight_decay, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):

@@ -11,6 +11,7 @@ import torch
 
 from . import ops, _lib
 from .ddp import GradAllReducer
+from .loss import prepare_inputs
 from .optim import FusedAdam
 
 
@@ -24,9 +25,7 @@ class TrainStep(object):
         net._ensure_flat()
         net.train()
         self.net = net
-        self.terms = tuple(float(t) for t in loss_terms)
-        self.softmax = bool(softmax)
-        self.loss_ext = loss_ext
+        self._pass = ops.LossPass(loss_terms, loss_ext, softmax)     # terms, loss_ext, softmax below read it: fixed for this object
         self.external_lr = optimizer is not None
         self.opt = optimizer if optimizer is not None else FusedAdam(net, lr, weight_decay=weight_decay)
         self.base_lr, self.milestones, self.gamma = lr, sorted(milestones), gamma
@@ -47,32 +46,33 @@ class TrainStep(object):
         self._half = torch.full((1,), 0.5, dtype=torch.float32, device=net.flat_params.device)
         self._loss_bufs = {}
 
+    terms = property(lambda self: self._pass.terms)
+    loss_ext = property(lambda self: self._pass.ext)
+    softmax = property(lambda self: self._pass.softmax)
+
     def _lr(self):
         return self.base_lr * self.gamma ** sum(1 for m in self.milestones if self.iteration >= m)
 
     def _loss_buffers(self, n, c, v, dev):
         key = (n, c, v)
         if key not in self._loss_bufs:
-            k, ncoef = (ops.loss_k(c), n * c * 2 + 2) if self.loss_ext is None else (ops.loss_ext_k(c), ops.loss_ext_ncoef(n, c))
-            self._loss_bufs[key] = (
-                torch.empty((n, ops.loss_rows(v), k), dtype=torch.float32, device=dev),
-                torch.empty(ncoef, dtype=torch.float32, device=dev))
+            k, _, ncoef = self._pass.sizes(n, c)
+            self._loss_bufs[key] = (torch.empty((n, ops.loss_rows(v), k), dtype=torch.float32, device=dev),
+                                    torch.empty(ncoef, dtype=torch.float32, device=dev))
         return self._loss_bufs[key]
 
-    def _loss_ext(self, logits, label, pw, iw, gscale, part, coef):
-        """the loss and its gradient through the second family's pass -> (out, dlogits)"""
-        from .loss import check_ext_inputs
-        check_ext_inputs(self.loss_ext, pw)
-        c = logits.shape[1]
-        cfg = ops.loss_ext_cfg(self.terms, self.loss_ext, c)
-        out = torch.empty(ops.loss_ext_nout(c), dtype=torch.float32, device=logits.device)
-        if self.dist_loss:
-            ops.seg_loss_ext_fwd_dist(logits, label, pw, iw, cfg, self.softmax, part, out, coef, self.group)
-        else:
-            ops.seg_loss_ext_fwd(logits, label, pw, iw, cfg, self.softmax, part, out, coef)
+    def _loss(self, logits, label, pw, iw, gscale, part, coef):
+        """the loss of either family over the full batch (of all ranks with dist_loss, read now: it may be switched between
+        steps) and its gradient -> (out, dlogits)"""
+        lp = self._pass
+        logits, label, pw, iw = prepare_inputs(lp, logits, label, pw, iw)
+        out = torch.empty(lp.sizes(logits.shape[0], logits.shape[1])[1], dtype=torch.float32, device=logits.device)
+        lp.forward(logits, label, pw, iw, part, out, coef, self.group, self.dist_loss)
         dlogits = torch.empty_like(logits)
-        ops.seg_loss_ext_bwd(logits, label, pw, coef, gscale, cfg, self.softmax, dlogits)
+        lp.backward(logits, label, pw, coef, gscale, dlogits)
         return out, dlogits
+
+    _loss_ext = _loss          # its name while the second family had a path of its own
 
     def _fwd_bwd(self, x, label, domain, pw, iw, gscale, gflat, reduce_hook, reuse_packs=False):
         net = self.net
@@ -80,34 +80,8 @@ class TrainStep(object):
         net._fwd_counter += 1
         logits, sv = net.engine.forward(x, domain, True, net.dropout_active(), net.dropout_seed, step, keep=True,
                                         reuse_packs=reuse_packs)
-        n, c = logits.shape[0], logits.shape[1]
-        v = logits[0, 0].numel()
-        if logits.shape != label.shape:                                       # as fplx.loss._FusedSegLoss.forward
-            raise ValueError("fplx loss: prediction {0:} and ground_truth {1:} differ in shape".format(
-                tuple(logits.shape), tuple(label.shape)))
-        if self.terms[2] != 0.0 and (pw is None or iw is None):
-            raise KeyError('pixel_weight')                                    # dice.py:109-110 index the dict
-        if self.terms[2] == 0.0:
-            iw = None
-        label = label.float().contiguous()
-        if pw is not None:
-            pw = pw.float().contiguous()
-            if pw.numel() != n * v:
-                raise ValueError("fplx loss: pixel_weight must be [N,1,D,H,W]")
-        if iw is not None:
-            iw = iw.float().contiguous()
-        part, coef = self._loss_buffers(n, c, v, logits.device)
-        if self.loss_ext is not None:
-            out, dlogits = self._loss_ext(logits, label, pw, iw, gscale, part, coef)
-            net.engine.backward(sv, dlogits, gflat, reduce_hook)
-            return out
-        out = torch.empty(4 + c, dtype=torch.float32, device=logits.device)
-        if self.dist_loss:
-            ops.seg_loss_fwd_dist(logits, label, pw, iw, self.terms, self.softmax, part, out, coef, self.group)
-        else:
-            ops.seg_loss_fwd(logits, label, pw, iw, self.terms, self.softmax, part, out, coef)
-        dlogits = torch.empty_like(logits)
-        ops.seg_loss_bwd(logits, label, pw, coef, gscale, self.terms, self.softmax, dlogits)
+        part, coef = self._loss_buffers(logits.shape[0], logits.shape[1], logits[0, 0].numel(), logits.device)
+        out, dlogits = self._loss(logits, label, pw, iw, gscale, part, coef)
         net.engine.backward(sv, dlogits, gflat, reduce_hook)
         return out
 

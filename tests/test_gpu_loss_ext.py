@@ -1,6 +1,7 @@
 """The second loss family on the GPU: the reference's fixtures through SegLossDictAll and through TrainStep's loss path, the exact
 and rounding-bound oracles of tests/lossoracle_ext.py, the split batch, GeneralizedCE's class and pixel weights against float64,
-and a SegmentationAgent run on the engine step."""
+a SegmentationAgent run on the engine step, and the second family's pass without a term of its own against the first family's pass,
+bit for bit."""
 import os
 
 import numpy as np
@@ -245,3 +246,82 @@ def test_agent_runs_new_losses_on_the_engine_step():
         assert np.isfinite(a["loss"]) and a["loss"] > 0
         assert abs(a["loss"] - b_["loss"]) < 1e-6 and np.abs(a["class_dice"] - b_["class_dice"]).max() < 1e-6
     assert float((pa - pb).abs().max()) <= 1e-6 * float(pb.abs().max())
+
+
+# ---------------------------------------------------------------- 6. no second-family term: the first family's pass
+
+def _bits(t):
+    return t.contiguous().view(torch.int32).cpu().numpy()
+
+
+# Where the two passes differ, and did before they shared any code (the two copies of the forward loop fuse differently at
+# C >= 3): the pixel-weighted intersection sums (column 6c + 2) and the CE numerator (column 6C) of single partial rows, by 1-2 ulp
+# of fp32, and what the finalize computes from them - out[2], Dice coefficients B (odd indices of coef).  part: (n, row, column);
+# out, coef: index.  Key: (n, c, v), softmax, weighted.  These entries must pass lossoracle.check_B on both sides; every other
+# entry is bitwise.  The gradient has no list: from the SAME coefficients the two backward kernels must give the same bits
+# everywhere, and from their own coefficients wherever those are bit-equal.
+DIFFERED_BEFORE = {
+    ((3, 3, 4099), True, True): dict(part=[(0, 0, 18), (1, 1, 18)]),
+    ((3, 3, 4099), False, False): dict(part=[(1, 1, 18)], out=[2]),
+    ((3, 3, 4099), False, True): dict(part=[(0, 1, 18), (1, 1, 18)]),
+    ((2, 8, 9001), True, True): dict(part=[(0, 0, 14), (0, 1, 14), (0, 1, 26), (0, 2, 2), (0, 2, 20), (1, 0, 38), (1, 1, 14)], coef=[5]),
+    ((2, 8, 9001), False, True): dict(part=[(0, 0, 20), (0, 0, 44), (0, 1, 32), (0, 1, 48), (0, 2, 14), (0, 2, 44), (1, 0, 2), (1, 0, 20),
+                                            (1, 2, 44)], coef=[15, 27]),
+}
+
+
+@pytest.mark.parametrize("ncv", [(1, 2, 37), (2, 1, 700), (3, 3, 4099), (2, 8, 9001)])
+@pytest.mark.parametrize("softmax", [True, False])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_zero_ext_weights_is_the_first_family(ncv, softmax, weighted):
+    """one short block, C = 1, two and three partial rows with ragged tails, odd N with odd K, C = MAXC; soft labels, real
+    predictions and non-dyadic weights, so every product rounds.  The sums, values, coefficients and gradient the two passes
+    share are compared as bit patterns, except at DIFFERED_BEFORE; the second family's backward is run once more on the first
+    family's coefficients, and that gradient is bitwise everywhere."""
+    from fplx import ops
+    n, c, v = ncv
+    key = "ext.same.%d.%d.%d" % ncv
+    xh = LO.real_logits(key, n, c, v) if softmax else LO.real_probs(key, n, c, v)
+    yh = LO.soft_labels(key + ".y", n, c, v)
+    g = LO.rng(key + ".w")
+    pwh = (g.random((n, v)) * 1.99 + 0.005).astype(np.float32) if weighted else None
+    iwh = (g.random(n) * 1.99 + 0.005).astype(np.float32) if weighted else None
+    x, y, pw, iw = _cuda(xh), _cuda(yh), _cuda(pwh), _cuda(iwh)
+    terms = (0.5, 0.3, 0.2 if weighted else 0.0, 0.1)
+    cfg = ops.loss_ext_cfg(terms, ((0.0,) * 7, ops.LOSS_EXT_DEFAULTS), c)
+    gs = torch.full((1,), 0.7, dtype=torch.float32, device="cuda")
+    rows, k0 = ops.loss_rows(v) - 5, 6 * c + 3
+    got = []
+    for k, nout, ncoef, fwd, bwd, how in (
+            (ops.loss_k(c), 4 + c, n * c * 2 + 2, ops.seg_loss_fwd, ops.seg_loss_bwd, terms),
+            (ops.loss_ext_k(c), ops.loss_ext_nout(c), ops.loss_ext_ncoef(n, c), ops.seg_loss_ext_fwd, ops.seg_loss_ext_bwd, cfg)):
+        part = torch.zeros((n, ops.loss_rows(v), k), dtype=torch.float32, device="cuda")
+        out = torch.zeros(nout, dtype=torch.float32, device="cuda")
+        coef = torch.zeros(ncoef, dtype=torch.float32, device="cuda")
+        dl = torch.zeros_like(x)
+        fwd(x, y, pw, iw, how, softmax, part, out, coef)
+        bwd(x, y, pw, coef, gs, how, softmax, dl)
+        torch.cuda.synchronize()
+        used = part.view(-1)[:n * rows * k].view(n, rows, k)[:, :, :k0]
+        got.append(dict(part=used, out=out[:4 + c], coef=coef[:n * c * 2 + 2].clone(), dlogits=dl))
+    coef[:n * c * 2 + 2] = got[0]["coef"]                  # the second family's backward on the first family's coefficients
+    dl_same = torch.zeros_like(x)
+    ops.seg_loss_ext_bwd(x, y, pw, coef, gs, cfg, softmax, dl_same)
+    torch.cuda.synchronize()
+    assert np.array_equal(_bits(dl_same), _bits(got[0]["dlogits"])), "equal coefficients, different gradient bits"
+    known = DIFFERED_BEFORE.get((ncv, softmax, weighted), {})
+    differ = {name: _bits(got[0][name]) != _bits(got[1][name]) for name in got[0]}
+    print("%s sm=%d w=%d: entries that differ %s" % (key, softmax, weighted, {k: int(m.sum()) for k, m in differ.items()}))
+    for name in ("part", "out", "coef"):
+        allowed = np.zeros_like(differ[name])
+        for i in known.get(name, ()):
+            allowed[i] = True
+        assert not (differ[name] & ~allowed).any(), (name, np.argwhere(differ[name] & ~allowed)[:8].tolist())
+    # from its own coefficients: bitwise unless a coefficient differs, then (as every listed entry) within the float64 bound
+    assert not differ["dlogits"].any() or differ["coef"].any(), np.argwhere(differ["dlogits"])[:8].tolist()
+    if known:
+        r = LO.reference(xh, yh, pwh, iwh, terms, softmax, gscale=0.7)
+        for side, t in zip(("first family", "second family"), got):
+            res = LO.check_B(r, out=t["out"].cpu().numpy(), dl=t["dlogits"].cpu().numpy(),
+                             sm=t["part"].double().sum(1).cpu().numpy(), what="%s %s" % (key, side))
+            print("   %s: error / bound %s" % (side, {k: "%.3g" % q for k, q in res.items()}))
