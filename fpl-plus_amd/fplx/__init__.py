@@ -9,10 +9,11 @@ from . import _lib
 _lib.lib()          # fail loudly, now, if the HIP extension is missing
 
 from .net import UNet2D5_dsbn                                      # noqa: E402
+from .nets3d import UNet2D5, UNet3D                                # noqa: E402
 from .dsbn import DomainSpecificBatchNorm3d                        # noqa: E402
 from .loss import (SegLossDict, DiceLoss, CrossEntropyLoss, DiceLoss_weight, CombinedLoss,  # noqa: E402
                    EntropyTerm, make_loss, SegLossDictAll, FocalDiceLoss, NoiseRobustDiceLoss, ExpLogLoss,
-                   GeneralizedCELoss, MAELoss, MSELoss, SLSRLoss)
+                   GeneralizedCELoss, MAELoss, MSELoss, SLSRLoss, DeepSuperviseLoss)
 from .infer import Inferer                                         # noqa: E402
 from .agent import SegmentationAgent, SegNetDict                   # noqa: E402
 from .optim import (FusedOptimizer, FusedAdam, FusedSGD, FusedAdadelta, FusedAdagrad, FusedAdamax, FusedASGD,  # noqa: E402
@@ -29,4 +30,4 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "FusedRMSprop", "FusedRprop", "get_optimizer", "get_lr_scheduler", "TrainStep",
            "parse_config", "synchronize_config", "filter", "ops", "ddp", "transform", "nifti", "evaluation", "NiftyDataset",
            "postprocess", "SegLossDictAll", "FocalDiceLoss", "NoiseRobustDiceLoss", "ExpLogLoss", "GeneralizedCELoss", "MAELoss",
-           "MSELoss", "SLSRLoss", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]
+           "MSELoss", "SLSRLoss", "DeepSuperviseLoss", "UNet2D5", "UNet3D", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]

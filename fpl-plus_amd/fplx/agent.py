@@ -35,13 +35,16 @@ from .infer import Inferer
 from .nifti import save_array_as_nifty_volume
 from .postprocess import PostProcessDict
 from .transform import TransformDict, Compose
-from .loss import SegLossDict, SegLossDictAll, make_loss
+from .loss import SegLossDict, SegLossDictAll, make_loss, DeepSuperviseLoss
 from .net import UNet2D5_dsbn
+from .nets3d import UNet2D5, UNet3D
 from .optim import get_optimizer, get_lr_scheduler
 
 SegNetDict = {
     'UNet2D5_dsbn': UNet2D5_dsbn,      # registry entry of the reference, net/net_dict_seg.py:44
     'UNet3D_dsbn': UNet2D5_dsbn,       # the all-3D configuration under its descriptive name
+    'UNet2D5': UNet2D5,                # net/net_dict_seg.py: the network the DSBN one was derived from (plain BatchNorm)
+    'UNet3D': UNet3D,                  # net/net_dict_seg.py: PyMIC's default 3D network (optional deep supervision)
 }
 
 
@@ -170,6 +173,10 @@ class SegmentationAgent(object):
             if net_name not in self.net_dict:
                 raise ValueError("Undefined network {0:}".format(net_name))  # agent_seg.py:86-87
             self.net = self.net_dict[net_name](self.config['network'])
+        if self.distributed and isinstance(self.net, (UNet2D5, UNet3D)):
+            raise ValueError("fplx: {0:} runs in a single process only - its gradients are not all-reduced and its parameters not "
+                             "broadcast under a torch.distributed group (data parallelism is built for UNet2D5_dsbn)".format(
+                                 type(self.net).__name__))
         if self.tensor_type != 'float':
             raise ValueError("fplx: tensor_type must be float (fp32 parameters)")
         self.net.float()
@@ -200,6 +207,12 @@ class SegmentationAgent(object):
         if self.loss_dict is None:
             self.loss_dict = SegLossDictAll
         self.loss_calculator = make_loss(self.config['training'], self.loss_dict, entropy_weight)
+        net_cfg = self.config.get('network', {})
+        if net_cfg.get('deep_supervise', False):                             # agent_seg.py:126-129
+            # (the key handed over is `deep_supervise_weight`; DeepSuperviseLoss reads `deep_suervise_weight`, as the
+            # reference's does - the weights are therefore always [1.0] * outputs)
+            weight = net_cfg.get('deep_supervise_weight', None)
+            self.loss_calculator = DeepSuperviseLoss({'deep_supervise_weight': weight, 'base_loss': self.loss_calculator})
         if self.distributed:
             self.loss_calculator.dist_sync = True                 # ONE loss over the full batch of all ranks
 
@@ -209,10 +222,11 @@ class SegmentationAgent(object):
     def get_loss_value(self, data, pred, gt, fpl_uda=False):
         """agent_seg.py:134-142"""
         d = {'prediction': pred, 'ground_truth': gt}
+        dev = (pred[0] if isinstance(pred, (list, tuple)) else pred).device
         if fpl_uda and data.get('pixel_weight', None) is not None:
-            d['pixel_weight'] = data['pixel_weight'].to(pred.device)
+            d['pixel_weight'] = data['pixel_weight'].to(dev)
             if data.get('image_weight', None) is not None:
-                d['image_weight'] = data['image_weight'].to(pred.device)
+                d['image_weight'] = data['image_weight'].to(dev)
         return self.loss_calculator(d)
 
     # ---- training loops
@@ -346,6 +360,8 @@ class SegmentationAgent(object):
             labels_prob = self.convert_tensor_type(data['label_prob']).to(self.device)
             outputs = self.inferer.run(self.net, inputs, domain * torch.ones(inputs.shape[0], dtype=torch.long))
             losses.append(float(self.get_loss_value(data, outputs, labels_prob).item()))
+            if isinstance(outputs, (list, tuple)):                            # agent_seg.py:542-543: deep supervision
+                outputs = outputs[0]
             hard = fpl_filter_mod.hard_label(outputs)                         # argmax on the device, uint8 [N,D,H,W]
             truth = fpl_filter_mod.hard_label(labels_prob)
             for i in range(inputs.shape[0]):                                  # get_classwise_dice of one-hot maps, fp32

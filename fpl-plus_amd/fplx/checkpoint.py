@@ -55,6 +55,14 @@ def reference_param_names(num_domains=2):
     return [k for k in reference_state_keys(num_domains) if k.rsplit(".", 1)[1] not in _BUFFERS]
 
 
+def param_names_of(net):
+    """the reference's net.parameters() order for `net`: by rule for UNet2D5_dsbn (dead twins included); UNet2D5 / UNet3D hold
+    exactly the reference's members in the reference's definition order and say so themselves (checked against the key list
+    dumped from the reference, tests/golden/ref_state_keys_nets3d.json)"""
+    own = getattr(net, "reference_param_names", None)
+    return own() if callable(own) else reference_param_names(net.num_domains)
+
+
 def _dead_default(key, live):
     """neutral tensor for a key that is dead in this configuration, shaped after its live sibling of the other
     dimensionality (a dim-3 level carries dead 2D twins and the other way round; the bilinear 1x1 convs are always dead)"""
@@ -92,6 +100,8 @@ def _dead_default(key, live):
 
 
 def reference_model_state_dict(net):
+    if callable(getattr(net, "reference_param_names", None)):          # UNet2D5 / UNet3D: no dead members, the reference's keys
+        return collections.OrderedDict((k, v.detach().cpu()) for k, v in net.state_dict().items())
     live = {k: v.detach().cpu() for k, v in net.state_dict().items()}
     dead = getattr(net, "_dead_state", None) or {}
     out = collections.OrderedDict()
@@ -140,7 +150,7 @@ def optimizer_to_reference(opt):
     segment that never stepped (torch creates state at a parameter's first gradient; Adagrad alone creates it at construction,
     so there it is step 0 and a zero sum) and nothing at all for SGD without momentum"""
     net = opt.net
-    names = reference_param_names(net.num_domains)
+    names = param_names_of(net)
     index = {k: i for i, k in enumerate(names)}
     active = opt._active_state()
     scalars = opt._segment_scalars()
@@ -170,7 +180,7 @@ def optimizer_to_reference(opt):
 
 def optimizer_from_reference(opt, sd):
     net = opt.net
-    names = reference_param_names(net.num_domains)
+    names = param_names_of(net)
     wrote = optimizer_name_of(sd)
     if wrote is not None and wrote != opt.TORCH:
         raise ValueError("fplx: this is a state of torch.optim.{0:}, the optimiser is {1:} (torch.optim.{2:})".format(

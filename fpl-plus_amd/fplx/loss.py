@@ -256,6 +256,52 @@ class CombinedLoss(AbstractSegLoss):
         self.ext, self.ext_params = tuple(ext), ext_params
 
 
+class DeepSuperviseLoss(AbstractSegLoss):
+    """loss/seg/deep_sup.py:7-41: the base loss once per output scale of a deep-supervised network on the shared ground truth and
+    weights, sum_i w_i loss_i / sum_i w_i.  `base_loss` is an fplx loss (one fused pass per scale).  The weights are read from
+    `deep_suervise_weight` (sic, deep_sup.py:21); the reference's agent passes `deep_supervise_weight` (agent_seg.py:126-129),
+    so through the agent they are always [1.0] * outputs - reproduced.  Not in SegLossDictAll, as in the reference.
+    `last_out` is the base loss's of output 0: the agent's train-time class Dice comes from the full-resolution output."""
+
+    def __init__(self, params):
+        super(DeepSuperviseLoss, self).__init__(params)
+        self.deep_sup_weight = params.get('deep_suervise_weight', None)
+        self.base_loss = params['base_loss']
+
+    @property
+    def dist_sync(self):
+        return self.__dict__.get('_dist_sync', False)
+
+    @dist_sync.setter
+    def dist_sync(self, on):                       # the full-batch evaluation is the base loss's business
+        self.__dict__['_dist_sync'] = on
+        base = self.__dict__.get('_modules', {}).get('base_loss')
+        if base is not None and hasattr(base, 'dist_sync'):
+            base.dist_sync = on
+
+    def forward(self, loss_input_dict):
+        predict = loss_input_dict['prediction']
+        if not isinstance(predict, (list, tuple)):
+            raise ValueError("""For deep supervision, the prediction should
+                be a list or a tuple""")
+        predict_num = len(predict)
+        if self.deep_sup_weight is None:
+            self.deep_sup_weight = [1.0] * predict_num
+        else:
+            assert (predict_num == len(self.deep_sup_weight))
+        loss_sum, weight_sum, first_out = 0.0, 0.0, None
+        scale = dict(loss_input_dict)
+        for i in range(predict_num):
+            scale['prediction'] = predict[i]
+            temp_loss = self.base_loss(scale)
+            if i == 0:
+                first_out = getattr(self.base_loss, 'last_out', None)
+            loss_sum = loss_sum + temp_loss * self.deep_sup_weight[i]
+            weight_sum += self.deep_sup_weight[i]
+        self.last_out = first_out
+        return loss_sum / weight_sum
+
+
 def make_loss(training_cfg, loss_dict=None, entropy_weight=0.0):
     """create_loss_calculator (net_run_dsbn/agent_seg.py:113-132) for the fused losses."""
     loss_dict = SegLossDict if loss_dict is None else loss_dict

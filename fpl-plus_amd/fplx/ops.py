@@ -419,6 +419,40 @@ def maxpool2_bwd(x, dy, dskip, dx, dims, c, pd=2):
          ptr(dx), ld_of(dx), n, d, h, w, c, dt_of(x), stream())
 
 
+def head_fwd(a, w, bias, logits, n, v, c, ncls):
+    """1x1x1 classification head (fplx_head_fwd): a NDHWC 2-D view [n * v, ld] (fp32 | bf16), w fp32 [ncls, c(, 1, 1, 1)],
+    logits fp32 planar [n, ncls, v] (contiguous)"""
+    call("fplx_head_fwd", ptr(a), ld_of(a), dt_of(a), ptr(w), ptr(bias), ptr(logits), int(n), int(v), int(c), int(ncls), stream())
+
+
+def head_dgrad(dlogits, w, da, n, v, c, ncls, accumulate=False):
+    """da = w^T dlogits in da's dtype; accumulate: added into da in place (the second consumer of a decoder level's output)"""
+    call("fplx_head_dgrad", ptr(dlogits), ptr(w), ptr(da), ld_of(da), dt_of(da), int(n), int(v), int(c), int(ncls),
+         1 if accumulate else 0, stream())
+
+
+def head_wgrad_ws_bytes(n, v, c, ncls):
+    return int(_lib.lib().fplx_head_wgrad_ws_bytes(int(n), int(v), int(c), int(ncls)))
+
+
+def head_wgrad(a, dlogits, dw, db, n, v, c, ncls, ws):
+    """dw fp32 [ncls, c], db fp32 [ncls] (or None) through ws (uint8, head_wgrad_ws_bytes)"""
+    call("fplx_head_wgrad", ptr(a), ld_of(a), dt_of(a), ptr(dlogits), ptr(dw), ptr(db), int(n), int(v), int(c), int(ncls),
+         ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream())
+
+
+def interp_fwd(x, y, nc, dims, f):
+    """trilinear interpolation by f in {2, 4, 8}, align_corners = False: fp32 planar [nc, d, h, w] -> [nc, f d, f h, f w]"""
+    d, h, w = dims
+    call("fplx_interp_fwd", ptr(x), ptr(y), int(nc), int(d), int(h), int(w), int(f), stream())
+
+
+def interp_bwd(dy, dx, nc, dims, f):
+    """the transpose of interp_fwd: dy [nc, f d, f h, f w] -> dx [nc, d, h, w] (dims = the COARSE extents)"""
+    d, h, w = dims
+    call("fplx_interp_bwd", ptr(dy), ptr(dx), int(nc), int(d), int(h), int(w), int(f), stream())
+
+
 def loss_rows(v):
     return _lib.lib().fplx_loss_rows(v)
 

@@ -350,6 +350,30 @@ int fplx_upsample2_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int n, 
 int fplx_upsample2_bwd(const void* dy, int64_t ldy, void* dx, int64_t ldx, int n, int d, int h, int w, int c, int dt, int sd,
                        fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ 1x1x1 classification head + deep-supervision interpolation
+ * (csrc/head.hip) UNet3D's out_conv and out_conv1..3 (PyMIC/pymic/net/net3d/unet3d.py:131-135) and the interpolate(...,
+ * mode='trilinear') that brings a coarse head's logits to full size (unet3d.py:152-158).
+ * a: NDHWC activation [n * v][lda] of dtype dt (lda >= c; rows 16-byte aligned: lda % 4 == 0 for fp32, % 8 for bf16 - lda = 2 c
+ * where a is the left half of a concat buffer); w fp32 [ncls][c]; bias fp32 [ncls] (may be NULL: zero); logits / dlogits fp32
+ * planar [n][ncls][v].  c: a multiple of 8 up to 512; 1 <= ncls <= 8.  Anything else: FPLX_E_BADSHAPE / _BADDTYPE / _NULL before
+ * any launch.  All sums in a fixed order, no atomics.
+ *   fwd     logits[n][k][v] = bias[k] + sum_c w[k][c] a[n][v][c], fp32, c ascending
+ *   dgrad   da[n][v][c] = sum_k w[k][c] dlogits[n][k][v] (k ascending), rounded to dt; accumulate != 0: da = da + that, in place
+ *   wgrad   dw[k][c] = sum_{n,v} dlogits a, db[k] = sum dlogits (db may be NULL); two stages through ws of
+ *           fplx_head_wgrad_ws_bytes(n, v, c, ncls) bytes (0: shape refused); too small: FPLX_E_WORKSPACE */
+int fplx_head_fwd(const void* a, int64_t lda, int dt, const float* w, const float* bias, float* logits, int n, int64_t v, int c,
+                  int ncls, fplx_stream_t stream);
+int fplx_head_dgrad(const float* dlogits, const float* w, void* da, int64_t lda, int dt, int n, int64_t v, int c, int ncls,
+                    int accumulate, fplx_stream_t stream);
+size_t fplx_head_wgrad_ws_bytes(int n, int64_t v, int c, int ncls);
+int fplx_head_wgrad(const void* a, int64_t lda, int dt, const float* dlogits, float* dw, float* db, int n, int64_t v, int c,
+                    int ncls, void* ws, size_t ws_bytes, fplx_stream_t stream);
+/* Trilinear interpolation, align_corners = False, by one integer factor f in {2, 4, 8} on all three axes (other factors:
+ * FPLX_E_BADSHAPE): x fp32 planar [nc][d][h][w] -> y [nc][f d][f h][f w].  ATen's rule: src = max((dst + 0.5) / f - 0.5, 0),
+ * upper neighbour clamped at the edge.  bwd: dx = the exact transpose applied to dy, as a gather in a fixed order (no atomics). */
+int fplx_interp_fwd(const float* x, float* y, int64_t nc, int d, int h, int w, int f, fplx_stream_t stream);
+int fplx_interp_bwd(const float* dy, float* dx, int64_t nc, int d, int h, int w, int f, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ segmentation loss
  * Fused softmax + Dice (loss/seg/dice.py:20-57, util.py:85-107) + cross entropy
  * (loss/seg/ce.py:23-44) + per-sample image-weighted Dice (dice.py:106-128) + entropy
