@@ -67,29 +67,27 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 #ifdef __HIPCC__
-// one element of torch.optim.Adam (get_optimizer.py:17) - shared by adam_k (elementwise.hip) and the fused Adam + weight-pack
-// kernel (conv_generic.hip) so that both form the same expression tree (same contractions): bit-identical parameters
-struct FplxAdamConst { float step_size, b1, b2, eps, wd, inv_sqrt_bc2, gscale, omb1, omb2; };      // omb: 1 - beta
-__device__ __forceinline__ void fplx_adam_elem(float& pi, float g, float& mi, float& vi, const FplxAdamConst& c) {
-  // every addition is written as an explicit fma and every product that feeds one stands alone: nothing is left for
-  // -ffp-contract to decide differently in a scalar and in a float4 context (it did: the two kernels differed in the last bit)
-  const float gi = fmaf(c.wd, pi, g * c.gscale);
-  mi = fmaf(c.b1, mi, c.omb1 * gi);
-  vi = fmaf(c.b2, vi, (c.omb2 * gi) * gi);
-  const float denom = fmaf(sqrtf(vi), c.inv_sqrt_bc2, c.eps);
-  pi = fmaf(-c.step_size, mi / denom, pi);
-}
-// one element of the reference's seven other optimisers (get_optimizer.py:13-34, torch's _single_tensor_* functions) - shared by
-// optim_k (elementwise.hip) and optim_pack27_multi (conv_generic.hip) under the same rule as fplx_adam_elem: every addition
-// that takes a product is an explicit fma, and every product that feeds one stands alone.  Division and sqrtf are the correctly
-// rounded defaults.  The constants are formed on the host (fplx_optim_consts below); k0..k4 mean per kind:
+// one element of the eight optimisers the reference can train with (get_optimizer.py:13-34, torch's _single_tensor_* functions) -
+// shared by optim_k (elementwise.hip) and optim_pack27_multi (conv_generic.hip) so that both form the same expression tree:
+// bit-identical parameters.  Every addition that takes a product is an explicit fma, and every product that feeds one stands
+// alone: nothing is left for -ffp-contract to decide differently in a scalar and in a float4 context (it did: two kernels
+// differed in the last bit).  Division and sqrtf are the correctly rounded defaults.  The constants are formed on the host
+// (fplx_optim_consts below); k0..k5 mean per kind:
 //   SGD       k0 momentum                                        Adadelta  k0 rho, k1 1 - rho, k2 eps
 //   Adagrad   lr = lr / (1 + (step - 1) lr_decay), k2 eps         Adamax    lr = lr / (1 - b1^step), k0 b1, k1 1 - b1, k2 eps, k3 b2
 //   ASGD      lr = eta, k0 = 1 - lambd eta, k3 mu                 RMSprop   k0 alpha, k1 1 - alpha, k2 eps, k3 momentum
 //   Rprop     k0 etaminus, k1 etaplus, k3 / k4 smallest / largest step size, first: step == 1 (prev = 0, step_size = lr)
-struct FplxOptimConst { float lr, wd, gscale, k0, k1, k2, k3, k4; int first; };
+//   Adam      lr = lr / (1 - b1^step), k0 b1, k1 1 - b1, k2 eps, k3 b2, k4 1 - b2, k5 1 / sqrt(1 - b2^step)
+struct FplxOptimConst { float lr, wd, gscale, k0, k1, k2, k3, k4, k5; int first; };
 __device__ __forceinline__ float fplx_optim_grad(float pi, float g, const FplxOptimConst& c) {
   return fmaf(c.wd, pi, g * c.gscale);
+}
+__device__ __forceinline__ void fplx_adam_elem(float& pi, float g, float& mi, float& vi, const FplxOptimConst& c) {
+  const float gi = fplx_optim_grad(pi, g, c);
+  mi = fmaf(c.k0, mi, c.k1 * gi);
+  vi = fmaf(c.k3, vi, (c.k4 * gi) * gi);
+  const float denom = fmaf(sqrtf(vi), c.k5, c.k2);
+  pi = fmaf(-c.lr, mi / denom, pi);
 }
 template <bool MOM>
 __device__ __forceinline__ void fplx_sgd_elem(float& pi, float g, float& buf, const FplxOptimConst& c) {
@@ -163,6 +161,7 @@ __device__ __forceinline__ void fplx_optim_elem(float& pi, float g, float& s0, f
   else if constexpr (KIND == FPLX_OPT_ADAMAX) fplx_adamax_elem(pi, g, s0, s1, c);
   else if constexpr (KIND == FPLX_OPT_ASGD) fplx_asgd_elem(pi, g, s0, c);
   else if constexpr (KIND == FPLX_OPT_RMSPROP) fplx_rmsprop_elem<NS == 2>(pi, g, s0, s1, c);
+  else if constexpr (KIND == FPLX_OPT_ADAM) fplx_adam_elem(pi, g, s0, s1, c);
   else fplx_rprop_elem(pi, g, s0, s1, c);
 }
 // a kind / state-count pair as a compile-time constant: FPLX_OPTIM_DISPATCH(kind, ns, LAUNCH) expands LAUNCH(KIND, NS)
@@ -176,19 +175,20 @@ __device__ __forceinline__ void fplx_optim_elem(float& pi, float g, float& s0, f
     case FPLX_OPT_ASGD * 4 + 1: X(FPLX_OPT_ASGD, 1); break;                    \
     case FPLX_OPT_RMSPROP * 4 + 1: X(FPLX_OPT_RMSPROP, 1); break;              \
     case FPLX_OPT_RMSPROP * 4 + 2: X(FPLX_OPT_RMSPROP, 2); break;              \
+    case FPLX_OPT_ADAM * 4 + 2: X(FPLX_OPT_ADAM, 2); break;                    \
     default: X(FPLX_OPT_RPROP, 2); break;                                      \
   }
 // host side of both entry points: checks kind / nhp / step / state pointers and forms the constants; the step-dependent
-// scalars in double, as fplx_adam_step forms lr / bc1.  *ns = number of state streams the launch touches.
+// scalars in double and rounded once.  *ns = number of state streams the launch touches.
 static inline int fplx_optim_consts(const char* who, int kind, const float* hp, int nhp, int step, float gscale, const void* s0,
                                     const void* s1, FplxOptimConst* c, int* ns) {
-  static const int want[FPLX_OPT_COUNT] = {3, 4, 4, 5, 4, 5, 5};
+  static const int want[FPLX_OPT_COUNT] = {3, 4, 4, 5, 4, 5, 5, 5};
   FPLX_REQUIRE(kind >= 0 && kind < FPLX_OPT_COUNT, FPLX_E_BADSHAPE, "%s: unknown optimiser kind %d (0..%d)", who, kind,
                FPLX_OPT_COUNT - 1);
   FPLX_REQUIRE(hp, FPLX_E_NULL, "%s: null hyper-parameter array", who);
   FPLX_REQUIRE(nhp == want[kind], FPLX_E_BADSHAPE, "%s: kind %d takes %d hyper-parameters, got %d", who, kind, want[kind], nhp);
   FPLX_REQUIRE(step >= 1, FPLX_E_BADSHAPE, "%s: step=%d (1-based)", who, step);
-  *c = {hp[0], 0.f, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, step == 1};
+  *c = {hp[0], 0.f, gscale, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, step == 1};
   int need = 2;
   switch (kind) {
     case FPLX_OPT_SGD:
@@ -213,6 +213,11 @@ static inline int fplx_optim_consts(const char* who, int kind, const float* hp, 
     case FPLX_OPT_RMSPROP:
       c->k0 = hp[1]; c->k1 = (float)(1.0 - (double)hp[1]); c->k2 = hp[2]; c->k3 = hp[3]; c->wd = hp[4];
       need = hp[3] > 0.f ? 2 : 1;
+      break;
+    case FPLX_OPT_ADAM:                            // 1 - beta in float, not double: tests/golden/adam_parent_digest.json pins the bits
+      c->lr = (float)((double)hp[0] / (1.0 - pow((double)hp[1], step)));
+      c->k0 = hp[1]; c->k1 = 1.f - hp[1]; c->k2 = hp[3]; c->k3 = hp[2]; c->k4 = 1.f - hp[2]; c->wd = hp[4];
+      c->k5 = (float)(1.0 / sqrt(1.0 - pow((double)hp[2], step)));
       break;
     default:
       c->k0 = hp[1]; c->k1 = hp[2]; c->k3 = hp[3]; c->k4 = hp[4];

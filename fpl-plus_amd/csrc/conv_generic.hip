@@ -383,83 +383,21 @@ __device__ __forceinline__ void pack27_from_lds(const bf16_t* lds, bf16_t* wf, b
       *reinterpret_cast<uint4*>(wb + ((int64_t)(26 - tap) * Cin + ci0 + ci_l) * Cout + co0 + 8 * half) = pk.u;
     }
 }
-// Adam + weight pack in ONE launch (round 5): the weights change only in the optimiser step, and every forward opened with
-// pack_conv_w27_tiled_multi re-reading all 22 M master weights (48 us at the head of the step, where nothing overlaps it).
-// Blocks [0, tiles): a pack tile (16 co x 32 ci x 27 taps) of one 3x3x3 layer - the block applies Adam to ITS 13 824
-// elements (p, g, m, v as float4 runs, the arithmetic of adam_k: fplx_adam_elem) and packs the updated values from LDS;
-// blocks [tiles, ...): the rest of the flat segment (biases, PReLU slopes, transposed convolutions, out_conv, the stem),
-// `gap` ranges of the table, 1024 elements per block.  Every element of the segment is updated exactly once.
+// Optimiser step + weight pack in ONE launch (round 5): the weights change only in the optimiser step, and every forward opened
+// with pack_conv_w27_tiled_multi re-reading all 22 M master weights (48 us at the head of the step, where nothing overlaps it).
+// Blocks [0, tiles): a pack tile (16 co x 32 ci x 27 taps) of one 3x3x3 layer - the block applies the update to ITS 13 824
+// elements (p, g and the kind's NS state streams as float4 runs, the arithmetic of optim_k: fplx_optim_elem) and packs the
+// updated values from LDS; blocks [tiles, ...): the rest of the flat segment (biases, PReLU slopes, transposed convolutions,
+// out_conv, the stem), `gap` ranges of the table, 1024 elements per block.  Every element of the segment is updated exactly once.
 constexpr int AP_MAXGAP = PK_MAX + 1, AP_GAPBLK = 1024;
-struct AdamPackTable {
-  float *p, *m, *v;
-  const float* g;
-  FplxAdamConst c;
-  int64_t off[PK_MAX];                 // element offset of layer e's weight inside the segment
-  bf16_t* wf[PK_MAX];
-  bf16_t* wb[PK_MAX];
-  float* stamp[PK_MAX];                // see pack27_tile
-  int cout[PK_MAX], cin[PK_MAX], first[PK_MAX + 1], n;
-  int64_t gstart[AP_MAXGAP], glen[AP_MAXGAP];
-  int gfirst[AP_MAXGAP + 1], ng;
-};
-__global__ void __launch_bounds__(256)
-adam_pack27_multi(const AdamPackTable t) {
-  const int b = (int)blockIdx.x;
-  if (b >= t.first[t.n]) {             // ---- a gap block: plain Adam on up to 1024 elements
-    const int gb = b - t.first[t.n];
-    int e = 0;
-    while (e + 1 < t.ng && gb >= t.gfirst[e + 1]) ++e;
-    const int64_t lo = (int64_t)(gb - t.gfirst[e]) * AP_GAPBLK, len = t.glen[e];
-#pragma unroll
-    for (int k = 0; k < AP_GAPBLK / 256; ++k) {
-      const int64_t i = lo + threadIdx.x + 256 * k;
-      if (i < len) {
-        const int64_t x = t.gstart[e] + i;
-        float pi = t.p[x], mi = t.m[x], vi = t.v[x];
-        fplx_adam_elem(pi, t.g[x], mi, vi, t.c);
-        t.m[x] = mi; t.v[x] = vi; t.p[x] = pi;
-      }
-    }
-    return;
-  }
-  int e = 0;
-  while (e + 1 < t.n && b >= t.first[e + 1]) ++e;
-  const int Cout = t.cout[e], Cin = t.cin[e], blk = b - t.first[e];
-  __shared__ bf16_t lds[PK_CO * PK_ROW];
-  const int ci_tiles = Cin / PK_CI;
-  const int co0 = (blk / ci_tiles) * PK_CO, ci0 = (blk % ci_tiles) * PK_CI;
-  constexpr int SEG4 = PK_CI * 27 / 4;
-  for (int i = threadIdx.x; i < PK_CO * SEG4; i += 256) {
-    const int co_l = i / SEG4, q = i % SEG4;
-    const int64_t x = t.off[e] + ((int64_t)(co0 + co_l) * Cin + ci0) * 27 + 4 * q;
-    float4 pv = *reinterpret_cast<const float4*>(t.p + x), mv = *reinterpret_cast<const float4*>(t.m + x);
-    float4 vv = *reinterpret_cast<const float4*>(t.v + x);
-    const float4 gv = *reinterpret_cast<const float4*>(t.g + x);
-    fplx_adam_elem(pv.x, gv.x, mv.x, vv.x, t.c);
-    fplx_adam_elem(pv.y, gv.y, mv.y, vv.y, t.c);
-    fplx_adam_elem(pv.z, gv.z, mv.z, vv.z, t.c);
-    fplx_adam_elem(pv.w, gv.w, mv.w, vv.w, t.c);
-    *reinterpret_cast<float4*>(t.m + x) = mv;
-    *reinterpret_cast<float4*>(t.v + x) = vv;
-    *reinterpret_cast<float4*>(t.p + x) = pv;
-    if (t.stamp[e] && q % PK_STAMP_Q == 0) t.stamp[e][(int64_t)blk * PK_STAMP + co_l * 2 + q / PK_STAMP_Q] = pv.x;
-    bf16_t* d = lds + co_l * PK_ROW + 4 * q;
-    Act<bf16_t>::st(d, pv.x); Act<bf16_t>::st(d + 1, pv.y); Act<bf16_t>::st(d + 2, pv.z); Act<bf16_t>::st(d + 3, pv.w);
-  }
-  __syncthreads();
-  pack27_from_lds(lds, t.wf[e], t.wb[e], Cout, Cin, co0, ci0);
-}
-
-// The same launch for the seven other optimisers (fplx_optim_pack_step): adam_pack27_multi with the element function swapped -
-// the table's layer / gap geometry, the stamps and the pack half (pack27_from_lds) are Adam's; NS state streams are touched.
 struct OptimPackTable {
   float *p, *s0, *s1;
   const float* g;
   FplxOptimConst c;
-  int64_t off[PK_MAX];
+  int64_t off[PK_MAX];                 // element offset of layer e's weight inside the segment
   bf16_t* wf[PK_MAX];
   bf16_t* wb[PK_MAX];
-  float* stamp[PK_MAX];
+  float* stamp[PK_MAX];                // see pack27_tile
   int cout[PK_MAX], cin[PK_MAX], first[PK_MAX + 1], n;
   int64_t gstart[AP_MAXGAP], glen[AP_MAXGAP];
   int gfirst[AP_MAXGAP + 1], ng;
@@ -761,9 +699,8 @@ int fplx_adam_pack_ok(int cout, int cin) {
   return fplx_knob(FPLX_K_PACK_TILED) != 0 && fplx_knob(FPLX_K_PACK_MULTI) != 0 && cin % PK_CI == 0 && cout % PK_CO == 0;
 }
 
-// layer / gap geometry of a fused update + pack launch (AdamPackTable and OptimPackTable carry the same fields)
-extern "C++" template <typename Table>
-static int fill_pack_table(const char* who, Table& t, int64_t n, int nl, const int64_t* off, const int* cout, const int* cin,
+// layer / gap geometry of a fused update + pack launch
+static int fill_pack_table(const char* who, OptimPackTable& t, int64_t n, int nl, const int64_t* off, const int* cout, const int* cin,
                            void* const* wf, void* const* wb, float* const* stamp) {
   t.n = nl;
   t.first[0] = 0;
@@ -791,44 +728,42 @@ static int fill_pack_table(const char* who, Table& t, int64_t n, int nl, const i
   return FPLX_OK;
 }
 
-int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                        float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
-                        const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream) {
-  FPLX_REQUIRE(p && g && m && v && off && cout && cin && wf && wb, FPLX_E_NULL, "adam_pack_step: null pointer");
-  FPLX_REQUIRE(n > 0 && step >= 1 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "adam_pack_step: n=%lld step=%d layers=%d (1..%d)",
-               (long long)n, step, nl, PK_MAX);
-  FPLX_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               FPLX_E_BADSHAPE, "adam_pack_step: the flat buffers must be 16-byte aligned");
-  AdamPackTable t;
-  t.p = p; t.g = g; t.m = m; t.v = v;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  t.c = {(float)((double)lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale, 1.f - beta1, 1.f - beta2};
-  const int rc = fill_pack_table("adam_pack_step", t, n, nl, off, cout, cin, wf, wb, stamp);
-  if (rc != FPLX_OK) return rc;
-  adam_pack27_multi<<<t.first[t.n] + t.gfirst[t.ng], 256, 0, (hipStream_t)stream>>>(t);
-  return fplx_check_launch("adam_pack_step");
-}
-
-int fplx_optim_pack_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
-                         float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin, void* const* wf,
-                         void* const* wb, float* const* stamp, fplx_stream_t stream) {
-  FPLX_REQUIRE(p && g && off && cout && cin && wf && wb, FPLX_E_NULL, "optim_pack_step: null pointer");
-  FPLX_REQUIRE(n > 0 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "optim_pack_step: n=%lld layers=%d (1..%d)", (long long)n, nl, PK_MAX);
+// both entry points of the fused step + pack; who: the name the error text carries
+static int optim_pack_step_as(const char* who, int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp,
+                              int nhp, int step, float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin,
+                              void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream) {
+  FPLX_REQUIRE(p && g && off && cout && cin && wf && wb, FPLX_E_NULL, "%s: null pointer", who);
+  FPLX_REQUIRE(n > 0 && nl > 0 && nl <= PK_MAX, FPLX_E_BADSHAPE, "%s: n=%lld layers=%d (1..%d)", who, (long long)n, nl, PK_MAX);
   OptimPackTable t;
   int ns = 0;
-  int rc = fplx_optim_consts("optim_pack_step", kind, hp, nhp, step, grad_scale, s0, s1, &t.c, &ns);
+  int rc = fplx_optim_consts(who, kind, hp, nhp, step, grad_scale, s0, s1, &t.c, &ns);
   if (rc != FPLX_OK) return rc;
   FPLX_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && (ns < 1 || ((uintptr_t)s0 % 16) == 0) &&
-               (ns < 2 || ((uintptr_t)s1 % 16) == 0), FPLX_E_BADSHAPE, "optim_pack_step: the flat buffers must be 16-byte aligned");
+               (ns < 2 || ((uintptr_t)s1 % 16) == 0), FPLX_E_BADSHAPE, "%s: the flat buffers must be 16-byte aligned", who);
   t.p = p; t.g = g; t.s0 = s0; t.s1 = s1;
-  rc = fill_pack_table("optim_pack_step", t, n, nl, off, cout, cin, wf, wb, stamp);
+  rc = fill_pack_table(who, t, n, nl, off, cout, cin, wf, wb, stamp);
   if (rc != FPLX_OK) return rc;
   const int grid = t.first[t.n] + t.gfirst[t.ng];
   hipStream_t st = (hipStream_t)stream;
 #define FPLX_OPTIM_LAUNCH(K, S) optim_pack27_multi<K, S><<<grid, 256, 0, st>>>(t)
   FPLX_OPTIM_DISPATCH(kind, ns, FPLX_OPTIM_LAUNCH)
 #undef FPLX_OPTIM_LAUNCH
-  return fplx_check_launch("optim_pack_step");
+  return fplx_check_launch(who);
+}
+
+int fplx_optim_pack_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                         float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin, void* const* wf,
+                         void* const* wb, float* const* stamp, fplx_stream_t stream) {
+  return optim_pack_step_as("optim_pack_step", kind, p, g, s0, s1, n, hp, nhp, step, grad_scale, nl, off, cout, cin, wf, wb, stamp,
+                            stream);
+}
+
+int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
+                        const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream) {
+  const float hp[5] = {lr, beta1, beta2, eps, weight_decay};
+  return optim_pack_step_as("adam_pack_step", FPLX_OPT_ADAM, p, g, m, v, n, hp, 5, step, grad_scale, nl, off, cout, cin, wf, wb,
+                            stamp, stream);
 }
 
 int fplx_pack_deconv_weight(const float* w, void* wf, void* wb, int cin, int cout, int dt, fplx_stream_t stream) {

@@ -911,21 +911,7 @@ pool_bwd_bn_reduce_col_k(const T* __restrict__ y, int64_t ldy, const T* __restri
 }
 
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(EW_THREADS)
-adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-       float step_size, float b1, float b2, float eps, float wd, float inv_sqrt_bc2, float gscale) {
-  const FplxAdamConst c = {step_size, b1, b2, eps, wd, inv_sqrt_bc2, gscale, 1.f - b1, 1.f - b2};
-  for (int64_t i = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * EW_THREADS) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    fplx_adam_elem(pi, g[i], mi, vi, c);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-
-
-// The seven other optimisers of get_optimizer (get_optimizer.py:13-34), one kernel per kind and state count: HBM-bound, so the
+// The optimisers of get_optimizer (get_optimizer.py:13-34), one kernel per kind and state count: HBM-bound, so the
 // aligned body moves one 16-byte vector per lane and stream (p, g and the NS state streams the kind has - nothing else is
 // touched), and a scalar head and tail take whatever is left of ANY n at ANY 4-byte-aligned base: the BN segments of the flat
 // buffer do not start on 16 bytes.  head: elements in front of p's first 16-byte boundary; VEC only if g and the state streams
@@ -1267,26 +1253,17 @@ int fplx_pool_bwd_bn_reduce(const void* y, int64_t ldy, const void* dy, int64_t 
   return fplx_check_launch("pool_bwd_bn_reduce");
 }
 
-int fplx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                   float eps, float weight_decay, int step, float grad_scale, fplx_stream_t stream) {
-  FPLX_REQUIRE(p && g && m && v, FPLX_E_NULL, "adam_step: null pointer");
-  FPLX_REQUIRE(n > 0 && step >= 1, FPLX_E_BADSHAPE, "adam_step: n=%lld step=%d", (long long)n, step);
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  adam_k<<<ew_grid(n), EW_THREADS, 0, (hipStream_t)stream>>>(p, g, m, v, n, (float)((double)lr / bc1), beta1, beta2, eps,
-                                                            weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale);
-  return fplx_check_launch("adam_step");
-}
-
-int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
-                    float grad_scale, fplx_stream_t stream) {
-  FPLX_REQUIRE(p && g, FPLX_E_NULL, "optim_step: null pointer");
-  FPLX_REQUIRE(n > 0, FPLX_E_BADSHAPE, "optim_step: n=%lld", (long long)n);
+// both entry points of the plain step; who: the name the error text carries
+static int optim_step_as(const char* who, int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp,
+                         int nhp, int step, float grad_scale, fplx_stream_t stream) {
+  FPLX_REQUIRE(p && g, FPLX_E_NULL, "%s: null pointer", who);
+  FPLX_REQUIRE(n > 0, FPLX_E_BADSHAPE, "%s: n=%lld", who, (long long)n);
   FplxOptimConst c;
   int ns = 0;
-  const int rc = fplx_optim_consts("optim_step", kind, hp, nhp, step, grad_scale, s0, s1, &c, &ns);
+  const int rc = fplx_optim_consts(who, kind, hp, nhp, step, grad_scale, s0, s1, &c, &ns);
   if (rc != FPLX_OK) return rc;
   FPLX_REQUIRE((uintptr_t)p % 4 == 0 && (uintptr_t)g % 4 == 0 && (ns < 1 || (uintptr_t)s0 % 4 == 0) && (ns < 2 || (uintptr_t)s1 % 4 == 0),
-               FPLX_E_BADSHAPE, "optim_step: the buffers must be 4-byte aligned");
+               FPLX_E_BADSHAPE, "%s: the buffers must be 4-byte aligned", who);
   const uintptr_t ph = (uintptr_t)p % 16;
   int64_t head = (int64_t)((16 - ph) % 16) / 4;
   if (head > n) head = n;
@@ -1301,7 +1278,18 @@ int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, in
   } while (0)
   FPLX_OPTIM_DISPATCH(kind, ns, FPLX_OPTIM_LAUNCH)
 #undef FPLX_OPTIM_LAUNCH
-  return fplx_check_launch("optim_step");
+  return fplx_check_launch(who);
+}
+
+int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
+                    float grad_scale, fplx_stream_t stream) {
+  return optim_step_as("optim_step", kind, p, g, s0, s1, n, hp, nhp, step, grad_scale, stream);
+}
+
+int fplx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                   float eps, float weight_decay, int step, float grad_scale, fplx_stream_t stream) {
+  const float hp[5] = {lr, beta1, beta2, eps, weight_decay};
+  return optim_step_as("adam_step", FPLX_OPT_ADAM, p, g, m, v, n, hp, 5, step, grad_scale, stream);
 }
 
 }  // extern "C"

@@ -608,36 +608,27 @@ class LossPass(object):
                                                                  self.softmax, dlogits)
 
 
-def adam_step(p, g, m, v, lr, step, weight_decay, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
-    call("fplx_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay,
-         int(step), grad_scale, stream())
-
-
 def adam_pack_ok(cout, cin):
     return _lib.lib().fplx_adam_pack_ok(int(cout), int(cin)) == 1
 
 
-def adam_pack_step(p, g, m, v, lr, step, weight_decay, grad_scale, betas, eps, layers):
-    """fplx_adam_step over the flat segment p AND the bf16 packs of the 3x3x3 weights inside it, one launch.
-    layers: [(element offset in p, cout, cin, wf, wb[, stamp])] ascending by offset (stamp: pack_conv_weights_batched)"""
-    import ctypes
-    n = len(layers)
-    vp, ip, lp = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_int64 * n
-    st = vp(*[(ptr(l[5]) or None) if len(l) > 5 else None for l in layers])
-    call("fplx_adam_pack_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, int(step),
-         grad_scale, n, lp(*[int(l[0]) for l in layers]), ip(*[int(l[1]) for l in layers]), ip(*[int(l[2]) for l in layers]),
-         vp(*[ptr(l[3]) for l in layers]), vp(*[ptr(l[4]) or None for l in layers]), st, stream())
-
-
-OPTIM_KINDS = ("SGD", "Adadelta", "Adagrad", "Adamax", "ASGD", "RMSprop", "Rprop")      # FPLX_OPT_* in include/fplx.h
+OPTIM_KINDS = ("SGD", "Adadelta", "Adagrad", "Adamax", "ASGD", "RMSprop", "Rprop", "Adam")      # FPLX_OPT_* in include/fplx.h
 
 
 def _optim_args(kind, p, g, s0, s1, hp, step, grad_scale):
-    import ctypes
     k = OPTIM_KINDS.index(kind) if isinstance(kind, str) else int(kind)
-    hp = [float(x) for x in hp]
-    return (k, ptr(p), ptr(g), ptr(s0) or None, ptr(s1) or None, p.numel(), (ctypes.c_float * len(hp))(*hp), len(hp),
+    return (k, ptr(p), ptr(g), ptr(s0) or None, ptr(s1) or None, p.numel(), (ctypes.c_float * len(hp))(*map(float, hp)), len(hp),
             int(step), grad_scale)
+
+
+def _pack_layer_args(layers):
+    """layers: [(element offset in p, cout, cin, wf, wb[, stamp])] ascending by offset (stamp: pack_conv_weights_batched)
+    -> nl, off, cout, cin, wf, wb, stamp of fplx_optim_pack_step"""
+    n = len(layers)
+    vp, ip, lp = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_int64 * n
+    off, cout, cin, wf, wb, stamp = zip(*[l if len(l) > 5 else tuple(l) + (None,) for l in layers])
+    dev = lambda ts: vp(*[None if t is None else t.data_ptr() for t in ts])       # one pass per column: this runs every step
+    return (n, lp(*map(int, off)), ip(*map(int, cout)), ip(*map(int, cin)), dev(wf), dev(wb), dev(stamp))
 
 
 def optim_step(kind, p, g, s0, s1, hp, step, grad_scale=1.0):
@@ -647,14 +638,17 @@ def optim_step(kind, p, g, s0, s1, hp, step, grad_scale=1.0):
 
 
 def optim_pack_step(kind, p, g, s0, s1, hp, step, grad_scale, layers):
-    """fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside p in one launch; layers as in adam_pack_step"""
-    import ctypes
-    n = len(layers)
-    vp, ip, lp = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_int64 * n
-    st = vp(*[(ptr(l[5]) or None) if len(l) > 5 else None for l in layers])
-    call("fplx_optim_pack_step", *(_optim_args(kind, p, g, s0, s1, hp, step, grad_scale) + (
-        n, lp(*[int(l[0]) for l in layers]), ip(*[int(l[1]) for l in layers]), ip(*[int(l[2]) for l in layers]),
-        vp(*[ptr(l[3]) for l in layers]), vp(*[ptr(l[4]) or None for l in layers]), st, stream())))
+    """fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside p in one launch; layers: see _pack_layer_args"""
+    call("fplx_optim_pack_step", *(_optim_args(kind, p, g, s0, s1, hp, step, grad_scale) + _pack_layer_args(layers) + (stream(),)))
+
+
+# Adam under its own two names (kind "Adam" of the above): a kernel timer that wraps ops by name reads these positional arguments
+def adam_step(p, g, m, v, lr, step, weight_decay, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8):
+    optim_step("Adam", p, g, m, v, (lr, betas[0], betas[1], eps, weight_decay), step, grad_scale)
+
+
+def adam_pack_step(p, g, m, v, lr, step, weight_decay, grad_scale, betas, eps, layers):
+    optim_pack_step("Adam", p, g, m, v, (lr, betas[0], betas[1], eps, weight_decay), step, grad_scale, layers)
 
 
 def mc_filter(logits_tcv, thr=0.01, want_hards=True, want_maps=False):

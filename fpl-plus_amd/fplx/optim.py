@@ -9,8 +9,8 @@ None are skipped entirely, exactly like torch's optimisers - with DSBN that is e
 the domains that took no part in the step (dsbn.py:56).
 
 FusedOptimizer holds what does not depend on the update rule (flat state buffers, segments and their step counts, the two
-entry points, the pack plan); FusedAdam and the seven classes behind get_optimizer's other names add the rule: which launch,
-which hyper-parameters, which state.
+entry points, the pack plan, the launch); the eight classes behind get_optimizer's names add the rule: which kind of
+fplx_optim_step, which hyper-parameters, which state.
 """
 import torch
 from torch.optim import Optimizer, lr_scheduler
@@ -23,9 +23,12 @@ def keyword_match(a, b):
 
 
 class FusedOptimizer(Optimizer):
-    """Base of the fused optimisers.  A subclass names torch's class (TORCH), lists its per-element state under torch's key
-    names (STATE; `_active_state()` where that depends on a hyper-parameter) and implements `_update`."""
+    """Base of the fused optimisers.  A subclass names torch's class (TORCH) and its kind of fplx_optim_step /
+    fplx_optim_pack_step (KIND, a name of ops.OPTIM_KINDS), lists its per-element state under torch's key names (STATE;
+    `_active_state()` where that depends on a hyper-parameter) and gives `_hp(si)`, the kind's hyper-parameters in the order
+    include/fplx.h documents."""
     TORCH = None
+    KIND = None
     STATE = ()
     HAS_STEP = True                      # torch keeps a `step` tensor per parameter (all but SGD)
 
@@ -55,10 +58,18 @@ class FusedOptimizer(Optimizer):
             setattr(self, name, b)
         return b
 
+    def _hp(self, si):
+        raise NotImplementedError
+
     def _update(self, si, start, end, g, plan):
         """one launch over flat_params[start:end] with the gradient g (same length) at segment si's current step count;
         plan: the engine's pack plan (the launch then writes the bf16 packs too) or None"""
-        raise NotImplementedError
+        st = [self._buffer(name)[start:end] for name in self._active_state()] + [None, None]
+        args = (self.KIND, self.net.flat_params[start:end], g, st[0], st[1], self._hp(si), self.seg_steps[si], self.grad_scale)
+        if plan:
+            ops.optim_pack_step(*(args + (plan,)))
+        else:
+            ops.optim_step(*args)
 
     def _segment_stepped(self, si):
         """after segment si's launch(es) of one step: per-segment host scalars (ASGD)"""
@@ -186,15 +197,20 @@ class FusedOptimizer(Optimizer):
 
 
 class FusedAdam(FusedOptimizer):
-    TORCH = "Adam"
+    """torch.optim.Adam(lr, weight_decay) (get_optimizer.py:16-17).  Its launches go through ops.adam_step / ops.adam_pack_step,
+    kind "Adam" under the names a kernel timer looks for."""
+    TORCH = KIND = "Adam"
     STATE = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super(FusedAdam, self).__init__(net, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
+    def _hp(self, si):
+        g = self.param_groups[0]
+        return (g['lr'], g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'])
+
     def _update(self, si, start, end, g, plan):
-        group = self.param_groups[0]
-        lr, (b1, b2), eps, wd = group['lr'], group['betas'], group['eps'], group['weight_decay']
+        lr, b1, b2, eps, wd = self._hp(si)
         args = (self.net.flat_params[start:end], g, self.exp_avg[start:end], self.exp_avg_sq[start:end], lr, self.seg_steps[si],
                 wd, self.grad_scale, (b1, b2), eps)
         if plan:
@@ -203,24 +219,7 @@ class FusedAdam(FusedOptimizer):
             ops.adam_step(*args)
 
 
-class _FusedKind(FusedOptimizer):
-    """the seven kinds of fplx_optim_step / fplx_optim_pack_step: a subclass gives KIND (ops.OPTIM_KINDS) and `_hp(si)`, the
-    kind's hyper-parameters in the order include/fplx.h documents"""
-    KIND = None
-
-    def _hp(self, si):
-        raise NotImplementedError
-
-    def _update(self, si, start, end, g, plan):
-        st = [self._buffer(name)[start:end] for name in self._active_state()] + [None, None]
-        args = (self.KIND, self.net.flat_params[start:end], g, st[0], st[1], self._hp(si), self.seg_steps[si], self.grad_scale)
-        if plan:
-            ops.optim_pack_step(*(args + (plan,)))
-        else:
-            ops.optim_step(*args)
-
-
-class FusedSGD(_FusedKind):
+class FusedSGD(FusedOptimizer):
     """torch.optim.SGD(lr, momentum, weight_decay) (get_optimizer.py:13-15): dampening 0, no Nesterov momentum"""
     TORCH = KIND = "SGD"
     STATE = ("momentum_buffer",)
@@ -237,7 +236,7 @@ class FusedSGD(_FusedKind):
         return (g['lr'], g['momentum'], g['weight_decay'])
 
 
-class FusedAdadelta(_FusedKind):
+class FusedAdadelta(FusedOptimizer):
     """torch.optim.Adadelta(lr, weight_decay) (get_optimizer.py:20-21)"""
     TORCH = KIND = "Adadelta"
     STATE = ("square_avg", "acc_delta")
@@ -250,7 +249,7 @@ class FusedAdadelta(_FusedKind):
         return (g['lr'], g['rho'], g['eps'], g['weight_decay'])
 
 
-class FusedAdagrad(_FusedKind):
+class FusedAdagrad(FusedOptimizer):
     """torch.optim.Adagrad(lr, weight_decay) (get_optimizer.py:22-23); the accumulator starts at 0"""
     TORCH = KIND = "Adagrad"
     STATE = ("sum",)
@@ -264,7 +263,7 @@ class FusedAdagrad(_FusedKind):
         return (g['lr'], g['lr_decay'], g['eps'], g['weight_decay'])
 
 
-class FusedAdamax(_FusedKind):
+class FusedAdamax(FusedOptimizer):
     """torch.optim.Adamax(lr, weight_decay) (get_optimizer.py:24-25)"""
     TORCH = KIND = "Adamax"
     STATE = ("exp_avg", "exp_inf")
@@ -282,7 +281,7 @@ def _f32(x):
     return float(torch.tensor(float(x), dtype=torch.float32))
 
 
-class FusedASGD(_FusedKind):
+class FusedASGD(FusedOptimizer):
     """torch.optim.ASGD(lr, weight_decay) (get_optimizer.py:26-27).  eta and mu are per-segment host scalars (seg_eta, seg_mu),
     float32 values like torch's state tensors: a step uses the pair formed after the previous one, from the lr of that time."""
     TORCH = KIND = "ASGD"
@@ -308,7 +307,7 @@ class FusedASGD(_FusedKind):
         self.seg_mu[si] = _f32(1 / max(1, step - g['t0']))
 
 
-class FusedRMSprop(_FusedKind):
+class FusedRMSprop(FusedOptimizer):
     """torch.optim.RMSprop(lr, momentum, weight_decay) (get_optimizer.py:30-32): not centred"""
     TORCH = KIND = "RMSprop"
     STATE = ("square_avg", "momentum_buffer")
@@ -325,7 +324,7 @@ class FusedRMSprop(_FusedKind):
         return (g['lr'], g['alpha'], g['eps'], g['momentum'], g['weight_decay'])
 
 
-class FusedRprop(_FusedKind):
+class FusedRprop(FusedOptimizer):
     """torch.optim.Rprop(lr) (get_optimizer.py:33-34): no weight decay; a segment's step_size is filled with the lr of its
     first step (the kernel does that at step 1)"""
     TORCH = KIND = "Rprop"

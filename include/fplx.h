@@ -464,7 +464,8 @@ int fplx_seg_loss_ext_bwd(const float* logits, const float* label, const float* 
 /* ------------------------------------------------------------------ optimiser
  * torch.optim.Adam(lr, weight_decay) as built by net_run_dsbn/get_optimizer.py:17 on a flat
  * fp32 buffer: g += wd*p; m,v moments; bias correction with `step` (1-based); p -= lr/bc1 * m/(sqrt(v)/sqrt(bc2)+eps).
- * grad_scale multiplies g first (1/world_size after an all-reduce sum). */
+ * grad_scale multiplies g first (1/world_size after an all-reduce sum).  This is fplx_optim_step (below) with kind
+ * FPLX_OPT_ADAM, s0 = m, s1 = v and hp = {lr, beta1, beta2, eps, weight_decay}: same kernel, same refusals. */
 int fplx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int step, float grad_scale, fplx_stream_t stream);
 /* fplx_adam_step over the flat segment [0, n) AND, in the same launch, the bf16 packs fplx_pack_conv_weights_batched makes
@@ -472,12 +473,13 @@ int fplx_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  * what the train step otherwise re-reads at the head of every forward, unet2d5_dsbn.py:54-55 + get_optimizer.py:17).
  * off[i]: element offset of layer i's [cout][cin][3][3][3] weight in the segment (ascending, multiples of 4); layers must
  * satisfy fplx_adam_pack_ok; wb[i] may be NULL; stamp: as in fplx_pack_conv_weights_batched (may be NULL), written from the
- * updated values.  Same parameters, moments and packs as the two separate calls, bit for bit. */
+ * updated values.  p, g, m and v must be 16-byte aligned.  Same parameters, moments and packs as the two separate calls,
+ * bit for bit.  This is fplx_optim_pack_step (below) with kind FPLX_OPT_ADAM, s0 = m, s1 = v and fplx_adam_step's hp. */
 int fplx_adam_pack_ok(int cout, int cin);
 int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int step, float grad_scale, int nl, const int64_t* off, const int* cout,
                         const int* cin, void* const* wf, void* const* wb, float* const* stamp, fplx_stream_t stream);
-/* The seven other optimisers get_optimizer can run (net_run_dsbn/get_optimizer.py:13-34; it passes lr, momentum and
+/* Every optimiser get_optimizer can run (net_run_dsbn/get_optimizer.py:13-34; it passes lr, momentum and
  * weight_decay only, everything else is torch's default), one launch over a flat fp32 segment, with the arithmetic of torch's
  * _single_tensor_* functions.  p, g, s0, s1: any 4-byte-aligned base, any n > 0.  hp: HOST array of nhp floats; s0 / s1: the
  * kind's state streams, read and written (a stream the kind does not have is never touched and may be NULL):
@@ -494,17 +496,19 @@ int fplx_adam_pack_step(float* p, const float* g, float* m, float* v, int64_t n,
  *                       (s1 only if momentum > 0; not centred)
  *   FPLX_OPT_RPROP      lr, etaminus, etaplus, step_min, step_max        prev             step_size       get_optimizer.py:33-34
  *                       (no weight decay; at step == 1 the incoming s0 / s1 are ignored: prev = 0, step_size = lr)
- * step (1-based) enters Adagrad's lr / (1 + (step - 1) lr_decay) and Adamax's lr / (1 - beta1^step), formed in double on the
- * host like fplx_adam_step's lr / bc1; grad_scale multiplies g first (for Rprop that keeps sign and zero, which is all it reads).
+ *   FPLX_OPT_ADAM       lr, beta1, beta2, eps, weight_decay              exp_avg          exp_avg_sq      get_optimizer.py:16-17
+ * step (1-based) enters Adagrad's lr / (1 + (step - 1) lr_decay), Adamax's and Adam's lr / (1 - beta1^step) and Adam's
+ * 1 / sqrt(1 - beta2^step), formed in double on the host and rounded once; grad_scale multiplies g first (for Rprop that keeps
+ * sign and zero, which is all it reads).
  * FPLX_E_BADSHAPE: unknown kind, n <= 0, step < 1, wrong nhp; FPLX_E_NULL: a missing pointer the kind needs. */
 enum { FPLX_OPT_SGD = 0, FPLX_OPT_ADADELTA, FPLX_OPT_ADAGRAD, FPLX_OPT_ADAMAX, FPLX_OPT_ASGD, FPLX_OPT_RMSPROP, FPLX_OPT_RPROP,
-       FPLX_OPT_COUNT };
+       FPLX_OPT_ADAM, FPLX_OPT_COUNT };
 int fplx_optim_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
                     float grad_scale, fplx_stream_t stream);
-/* fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside the segment in one launch: fplx_adam_pack_step with the
- * element function swapped (same table, same layer rules - fplx_adam_pack_ok -, same stamps); p, g and the kind's state
- * streams must be 16-byte aligned.  Same parameters, state and packs as fplx_optim_step followed by
- * fplx_pack_conv_weights_batched, bit for bit. */
+/* fplx_optim_step AND the bf16 packs of the 3x3x3 weights inside the segment in one launch: nl, off, cout, cin, wf, wb and
+ * stamp as fplx_adam_pack_step describes them (layer rule: fplx_adam_pack_ok); p, g and the kind's state streams must be
+ * 16-byte aligned.  Same parameters, state and packs as fplx_optim_step followed by fplx_pack_conv_weights_batched, bit for
+ * bit. */
 int fplx_optim_pack_step(int kind, float* p, const float* g, float* s0, float* s1, int64_t n, const float* hp, int nhp, int step,
                          float grad_scale, int nl, const int64_t* off, const int* cout, const int* cin, void* const* wf,
                          void* const* wb, float* const* stamp, fplx_stream_t stream);

@@ -1,5 +1,5 @@
-"""Oracles for the seven optimiser kinds of fplx_optim_step (SGD, Adadelta, Adagrad, Adamax, ASGD, RMSprop, Rprop), in the manner
-of lossoracle.adam_ref: one step from fp32 state, evaluated in float64, with a per-element bound for every output.
+"""Oracles for seven of the eight optimiser kinds of fplx_optim_step (SGD, Adadelta, Adagrad, Adamax, ASGD, RMSprop, Rprop; the
+eighth, Adam, has lossoracle.adam_ref and the recorded bits of tests/golden/adam_parent_digest.json), in the manner of adam_ref: one step from fp32 state, evaluated in float64, with a per-element bound for every output.
 
 Conventions.  u = U = 2^-24: one correctly rounded fp32 operation (+, x, /, sqrt, fma) errs by at most u |result|; ETA = 2^-126
 covers a result in the denormal range.  Hyper-parameters are taken as the floats that cross the C ABI (`f32`): the rounding of a

@@ -348,19 +348,31 @@ def test_hard_label_against_numpy(c, n):
 
 # ---------------------------------------------------------------- Adam
 
-def _adam_case(n, steps, gscale, wd, zero=False):
+def _place(a, mode):
+    """a on the device at a 16-byte-aligned base ('a') or one float behind one ('o')"""
+    buf = torch.zeros(a.size + 8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    off = 1 if mode == "o" else 0
+    v = buf[off:off + a.size]
+    v.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    return v
+
+
+def _adam_case(n, steps, gscale, wd, zero=False, modes="aaaa"):
+    """modes: placement of p, g, m, v - 'aaaa' the 16-byte body, 'oooo' scalar head + body + tail, 'oaoo' (p and g on different
+    alignments) the all-scalar kernel"""
     from fplx import ops
     g = O.rng("adam.%d.%g.%g" % (n, gscale, wd))
-    p = torch.from_numpy(g.standard_normal(n).astype(np.float32)).cuda()
-    m = torch.zeros(n, device="cuda")
-    v = torch.zeros(n, device="cuda")
+    p = _place(g.standard_normal(n).astype(np.float32), modes[0])
+    m = _place(np.zeros(n, np.float32), modes[2])
+    v = _place(np.zeros(n, np.float32), modes[3])
     if steps[0] > 1 and not zero:                                       # a state as it is late in training
-        m = torch.from_numpy((g.standard_normal(n) * 1e-2).astype(np.float32)).cuda()
-        v = torch.from_numpy((g.random(n) * 1e-4).astype(np.float32)).cuda()
+        m.copy_(torch.from_numpy((g.standard_normal(n) * 1e-2).astype(np.float32)))
+        v.copy_(torch.from_numpy((g.random(n) * 1e-4).astype(np.float32)))
     worst = {}
     for step in steps:
         gr = np.zeros(n, np.float32) if zero else (g.standard_normal(n) * 10.0 ** g.integers(-6, 1)).astype(np.float32)
-        gd = torch.from_numpy(gr).cuda()
+        gd = _place(gr, modes[1])
         before = [t.cpu().numpy() for t in (p, m, v)]
         ops.adam_step(p, gd, m, v, 1e-3, step, wd, gscale)
         torch.cuda.synchronize()
@@ -370,18 +382,19 @@ def _adam_case(n, steps, gscale, wd, zero=False):
             assert np.array_equal(p.cpu().numpy(), before[0]) and not m.any() and not v.any()
         for k, x in res.items():
             worst[k] = max(worst.get(k, 0.0), x)
-    _log("adam n=%d steps=%s grad_scale=%g wd=%g zero=%d" % (n, list(steps), gscale, wd, zero), worst)
+    _log("adam n=%d steps=%s grad_scale=%g wd=%g zero=%d %s" % (n, list(steps), gscale, wd, zero, modes), worst)
     assert all(x <= 1.0 for x in worst.values()), worst
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 10007])
 def test_adam_step_against_float64(n):
-    for gscale in (1.0, 0.125):
-        for wd in (0.0, 1e-5):
-            _adam_case(n, (1, 2, 3, 4, 5), gscale, wd)
-            _adam_case(n, (1000, 100000), gscale, wd)
-    _adam_case(n, (1, 2), 1.0, 0.0, zero=True)
-    _adam_case(n, (1, 1000), 0.125, 1e-5, zero=True)
+    for modes in ("aaaa", "oooo", "oaoo"):
+        for gscale in (1.0, 0.125):
+            for wd in (0.0, 1e-5):
+                _adam_case(n, (1, 2, 3, 4, 5), gscale, wd, modes=modes)
+                _adam_case(n, (1000, 100000), gscale, wd, modes=modes)
+        _adam_case(n, (1, 2), 1.0, 0.0, zero=True, modes=modes)
+        _adam_case(n, (1, 1000), 0.125, 1e-5, zero=True, modes=modes)
 
 
 def test_adam_step_against_float64_full_size():

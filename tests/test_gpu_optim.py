@@ -1,7 +1,8 @@
 """-m gpu: the seven optimiser kinds of fplx_optim_step / fplx_optim_pack_step and the classes on top of them (fplx/optim.py)
 against tests/optimoracle.py: the float64 bound on random data (Rprop: bitwise), torch bit for bit on the exact data, zero
 gradients, the pack-fused launch against update + pack, TrainStep and SegmentationAgent with a foreign-to-Adam optimiser,
-checkpoints both ways, and the ABI's refusals."""
+checkpoints both ways, the ABI's refusals, and the eighth kind, Adam, bit for bit against the record of the kernels it had before
+it joined the family (its bound: tests/test_gpu_loss_exact.py)."""
 import os
 
 import numpy as np
@@ -336,14 +337,50 @@ def test_checkpoint_round_trip_and_torch_interop(kind):
             opt.load_state_dict(adam.state_dict())
 
 
+def _adam_recorder():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("record_adam_digest", os.path.join(root, "tools", "record_adam_digest.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("abi", [False, True])
+def test_adam_bits_equal_the_recorded_parent(abi):
+    """Adam is kind FPLX_OPT_ADAM of fplx_optim_step / fplx_optim_pack_step; before that it had kernels of its own.  The cases of
+    tools/record_adam_digest.py (adam_step at an aligned base and one float behind one - vector body / scalar head and tail now,
+    one scalar loop then -, adam_pack_step with stamps), through fplx.ops and through the two C entry points themselves: every
+    output after every step has the sha256 recorded from the commit before the change (tests/golden/adam_parent_digest.json)."""
+    import json
+    from fplx import ops
+    R = _adam_recorder()
+    with open(R.FIXTURE) as f:
+        want = json.load(f)
+    for behind in (0, 1):
+        inputs, out = R.step_case(ops, O.rng, behind, abi)
+        assert inputs == want["adam_step"]["inputs"], "the inputs drifted, not the kernel"
+        assert out == want["adam_step"]["outputs"], (behind, [a == b for a, b in zip(out, want["adam_step"]["outputs"])])
+    inputs, out = R.pack_case(ops, O.rng, abi)
+    assert inputs == want["adam_pack_step"]["inputs"], "the inputs drifted, not the kernel"
+    assert out == want["adam_pack_step"]["outputs"], [a == b for a, b in zip(out, want["adam_pack_step"]["outputs"])]
+
+
 def test_abi_refusals():
     from fplx import ops
     p, g, a, b = [torch.zeros(64, device="cuda") for _ in range(4)]
     hp = (1e-3, 0.9, 0.0)
     ops.optim_step("SGD", p, g, a, None, hp, 1)
-    for kind in (-1, 7):
+    for kind in (-1, len(ops.OPTIM_KINDS)):
         with pytest.raises(ValueError, match="kind"):
             ops.optim_step(kind, p, g, a, b, hp, 1)
+    adam = (1e-3, 0.9, 0.999, 1e-8, 0.0)
+    with pytest.raises(ValueError, match="state"):
+        ops.optim_step("Adam", p, g, a, None, adam, 1)
+    with pytest.raises(ValueError, match="hyper-parameters"):
+        ops.optim_step("Adam", p, g, a, b, adam[:4], 1)
+    with pytest.raises(ValueError, match="step"):
+        ops.optim_step("Adam", p, g, a, b, adam, 0)
     with pytest.raises(ValueError, match="step"):
         ops.optim_step("SGD", p, g, a, None, hp, 0)
     with pytest.raises(ValueError, match="state"):

@@ -166,7 +166,9 @@ def test_abi_refusals_need_no_device():
         return rc, _lib.last_error()
 
     sgd, adamax = (1e-3, 0.9, 0.0), (1e-3, 0.9, 0.999, 1e-8, 0.0)
-    for args, rc, word in (((7, P, P, P, P, 8, sgd, 1), -1, "kind"), ((-1, P, P, P, P, 8, sgd, 1), -1, "kind"),
+    for args, rc, word in (((8, P, P, P, P, 8, sgd, 1), -1, "unknown optimiser kind"), ((-1, P, P, P, P, 8, sgd, 1), -1, "kind"),
+                           ((7, P, P, P, None, 8, adamax, 1), -5, "state"), ((7, P, P, P, P, 8, adamax[:4], 1), -1, "hyper"),
+                           ((7, P, P, P, P, 8, adamax, 0), -1, "step"),                  # kind 7, Adam: Adamax's five
                            ((0, P, P, P, None, 8, sgd, 0), -1, "step"), ((0, P, P, None, None, 8, sgd, 1), -5, "state"),
                            ((3, P, P, P, None, 8, adamax, 1), -5, "state"), ((0, P, P, P, None, 8, sgd + (0.0,), 1), -1, "hyper"),
                            ((0, P, P, None, None, 0, (1e-3, 0.0, 0.0), 1), -1, "n=0"),

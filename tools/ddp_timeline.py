@@ -91,9 +91,9 @@ def analyze(path):
         name = r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "")
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name))
     rows.sort()
-    adam = [i for i, r in enumerate(rows) if r[2].startswith("adam_pack27_multi") or r[2].startswith("adam_k")]
-    # iterations: between consecutive shared-segment optimiser launches (adam_pack27_multi); fall back to every second adam_k
-    cuts = [i for i in adam if rows[i][2].startswith("adam_pack27_multi")] or adam[::3]
+    adam = [i for i, r in enumerate(rows) if r[2].startswith("optim_pack27_multi") or r[2].startswith("optim_k")]
+    # iterations: between consecutive shared-segment optimiser launches (optim_pack27_multi); fall back to every third optim_k
+    cuts = [i for i in adam if rows[i][2].startswith("optim_pack27_multi")] or adam[::3]
     print("iteration | RCCL kernels | first RCCL start - iteration start (ms) | last backward kernel end (ms) | RCCL kernels started before it | last RCCL end (ms)")
     for a, b in zip(cuts[:-1], cuts[1:]):
         it = rows[a + 1:b]

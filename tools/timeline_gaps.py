@@ -20,7 +20,7 @@ stem = [s for s, e, q, n in rows if n.startswith("stem_fwd")]
 if len(stem) > nsteps:
     t0, t1 = stem[-nsteps - 1], stem[-1] - 1
 else:
-    adam = [e for s, e, q, n in rows if n.startswith("adam_k")]
+    adam = [e for s, e, q, n in rows if n.startswith("optim_k")]
     t0, t1 = adam[-2 * nsteps - 1], adam[-1]
 rows = [r for r in rows if r[0] >= t0 and r[1] <= t1]
 span = rows[-1][1] - rows[0][0]
