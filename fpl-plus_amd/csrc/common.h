@@ -289,7 +289,7 @@ inline void fplx_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
   X(OUTCONV_DGRAD_ROWS, "outconv_dgrad_rows", 1) /* fused out_conv backward as a stream of row segments (outconv_dgrad_rows); 0: the tile kernel (A/B, tested both ways) */ \
   X(PACK_TILED, "pack_tiled", 1)                                                                                       \
   X(PACK_MULTI, "pack_multi", 1)                                                                                       \
-  X(MARCH, "march", 1)                     /* 0: previous-generation stream kernels; 2: Cin = 32 march only */          \
+  X(MARCH, "march", 1)                     /* 0: no depth-march kernel (brick, tile / direct take the layers) */      \
   X(MARCH64_FW, "march64_fw", 0)           /* 16 / 32: force the footprint of the Cin = 64 march */                     \
   X(MARCH_DS, "march_ds", 0)               /* > 0: force the depth split of the march kernels */                        \
   X(MARCH128, "march128", 1)                                                                                           \
@@ -314,8 +314,6 @@ inline void fplx_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
   X(WG_VOX_LW, "wg_vox_lw", 1)             /* loader-wave voxel-GEMM weight gradient: 1 volumes <= 2048 voxels, 2 everywhere, 0 never */ \
   X(WG_VOX_CUS, "wg_vox_cus", 128)         /* blocks the voxel-GEMM weight gradient aims at: HALF the CUs - the main stream's deep-level kernels are small latency-bound grids that need free CUs at once (step -0.9 % against 256) */ \
   X(WG_VOX_MAXV, "wg_vox_maxv", 10000)     /* largest voxel count (whole batch) the voxel-GEMM weight gradient takes */    \
-  X(STREAM_MIN_W, "stream_min_w", 64)                                                                                  \
-  X(TILE_MT, "tile_mt", 0)                                                                                             \
   X(TILE_NT, "tile_nt", 0)                                                                                             \
   X(TILE_KS, "tile_ks", 0)                                                                                             \
   X(MID_TILE, "mid_tile", 1)                                                                                           \

@@ -1525,8 +1525,8 @@ conv_fwd_march64_lw(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __r
 
 struct MarchCfg { int tilesH, tilesW, dsegs, dlen, nblk, fw; };
 
-inline int march_enabled() {
-  return (int)fplx_knob(FPLX_K_MARCH);                    // tuning knob (benchmarks only): 0 = previous kernel
+inline bool march_enabled() {
+  return fplx_knob(FPLX_K_MARCH) != 0;                    // tuning knob (benchmarks only): 0 = no march kernel
 }
 
 inline MarchCfg march_cfg(int n, int d, int h, int w, int cin, int cout) {
@@ -1567,13 +1567,12 @@ inline MarchCfg march_cfg(int n, int d, int h, int w, int cin, int cout) {
 }  // namespace
 
 extern "C" int fplx_march_ok(int n, int d, int h, int w, int cin, int cout) {
-  const int en = march_enabled();                            // 1: both kernels, 2: Cin = 32 only
-  if (!en || cout % 32 != 0 || d < 4 || w < 64) return 0;
+  if (!march_enabled() || cout % 32 != 0 || d < 4 || w < 64) return 0;
   if (cin == 32) return h >= 16;
-  if (cin == 64) return en == 1 && h >= 8 && (int64_t)h * w * 64 * 2 < (int64_t)1 << 31;
+  if (cin == 64) return h >= 8 && (int64_t)h * w * 64 * 2 < (int64_t)1 << 31;
   if (cin == 128) {                                          // streamed-weight form of the Cin = 64 kernel
     const int k128 = (int)fplx_knob(FPLX_K_MARCH128);        // A/B knob
-    return k128 && en == 1 && h >= 8 && (int64_t)h * w * 128 * 2 < (int64_t)1 << 31;
+    return k128 && h >= 8 && (int64_t)h * w * 128 * 2 < (int64_t)1 << 31;
   }
   return 0;
 }

@@ -1431,262 +1431,21 @@ inline DwCfg dw_cfg(int n, int d, int h, int w, int cin, int cout) {
 }
 
 // ------------------------------------------------------------------------------------------
-// conv_fwd_stream: the previous-generation slab kernel (Cin in {32, 64}, large H x W); the depth-marching kernels of
-// conv_march.hip take these shapes first, this one remains for what they refuse and for A/B runs (FPLX_MARCH=0).
-// One block = an 8 x 32
-// output footprint in (h, w) x 32 output channels, marching along d:
-//   * three input slabs (10 x 34 voxels x Cin, 1-voxel halo, zero fill = padding) form a ring in
-//     LDS; every slab is fetched from HBM/L2 once per block and feeds 27 taps x 3 output depths;
-//     the next slab travels global -> registers while the current depth is computed and is
-//     written to LDS behind the depth's last barrier (async-stage split);
-//   * the weights of GT taps at a time stream L2 -> registers -> a two-buffer LDS ring, one
-//     barrier per group;
-//   * LDS rows are 16-byte-chunk XOR-swizzled so that every ds_read_b128 of an operand fragment
-//     (32 voxels / 32 output channels x 16 B) is bank-conflict free;
-//   * epilogue per depth: bias, bf16 store, per-channel sum / sum of squares kept in registers and
-//     written once per block (DSBN statistics, fixed order).
-template <int CIN>
-struct StreamGeo {
-  static constexpr int ROWB = CIN * 2, CH = ROWB / 16;
-  static constexpr int SW = 34, SH = 10, SLAB = SW * SH;
-  // Cin = 32: all 27 taps of the block's 32 output channels stay resident in LDS (55 KB) and the slab ring
-  // has a 4th slot, so one barrier per depth suffices.  Cin = 64: 3 taps at a time through a 2-buffer ring.
-  static constexpr int GT = CIN == 32 ? 27 : 3, NG = 27 / GT;
-  static constexpr int NSLOT = CIN == 32 ? 4 : 3, NWBUF = NG == 1 ? 1 : 2;
-  static constexpr int SLAB_BYTES = SLAB * ROWB, WBUF_BYTES = GT * 32 * ROWB;
-  static constexpr int NLD = (SLAB * CH + 255) / 256, NLW = NG == 1 ? 1 : (GT * 32 * CH + 255) / 256;
-  static constexpr int LDS = NSLOT * SLAB_BYTES + NWBUF * WBUF_BYTES;
-  static __device__ __forceinline__ int swz(int row) { return (row / (16 / CH)) % CH; }
-};
-
-template <int CIN>
-__global__ void __launch_bounds__(256)
-conv_fwd_stream(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ wp,
-                const float* __restrict__ bias, bf16_t* __restrict__ y, int64_t ldy, int N, int D, int H, int W,
-                int Cout, float* __restrict__ stats, int tilesH, int tilesW, int dsegs, int dlen) {
-  typedef StreamGeo<CIN> G;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* slabs = smem;
-  char* wbuf = smem + G::NSLOT * G::SLAB_BYTES;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, khalf = lane >> 5;
-  int b = blockIdx.x;
-  const int seg = b % dsegs; b /= dsegs;
-  const int tw = b % tilesW; b /= tilesW;
-  const int th = b % tilesH; b /= tilesH;
-  const int n = b;
-  const int h0 = th * 8, w0 = tw * 32, d0 = seg * dlen;
-  const int d1 = (d0 + dlen < D) ? d0 + dlen : D;
-  const int n0 = blockIdx.y * 32;
-
-  uint4 sreg[G::NLD], wreg[G::NLW];
-  auto slab_fetch = [&](int d) {                 // global -> registers (zero outside the volume)
-    const bool dok = d >= 0 && d < D;
-#pragma unroll
-    for (int k = 0; k < G::NLD; ++k) {
-      const int i = tid + k * 256;
-      const int vox = i / G::CH, c = i % G::CH;
-      const int hh = vox / G::SW + h0 - 1, ww = vox % G::SW + w0 - 1;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (i < G::SLAB * G::CH && dok && hh >= 0 && hh < H && ww >= 0 && ww < W)
-        v = *reinterpret_cast<const uint4*>(x + ((((int64_t)n * D + d) * H + hh) * W + ww) * ldx + c * 8);
-      sreg[k] = v;
-    }
-  };
-  auto slab_commit = [&](int d) {                // registers -> LDS slot of depth d
-    char* dst = slabs + ((d + 1) % G::NSLOT) * G::SLAB_BYTES;
-#pragma unroll
-    for (int k = 0; k < G::NLD; ++k) {
-      const int i = tid + k * 256;
-      const int vox = i / G::CH, c = i % G::CH;
-      if (i < G::SLAB * G::CH) *reinterpret_cast<uint4*>(dst + vox * G::ROWB + ((c ^ G::swz(vox)) * 16)) = sreg[k];
-    }
-  };
-  auto w_fetch = [&](int g) {
-#pragma unroll
-    for (int k = 0; k < G::NLW; ++k) {
-      const int i = tid + k * 256;
-      const int row = i / G::CH, c = i % G::CH;                 // row = tap_local * 32 + co
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (i < G::GT * 32 * G::CH)
-        v = *reinterpret_cast<const uint4*>(wp + ((int64_t)(g * G::GT + (row >> 5)) * Cout + n0 + (row & 31)) * CIN + c * 8);
-      wreg[k] = v;
-    }
-  };
-  auto w_commit = [&](int g) {
-    char* dst = wbuf + (g & 1) * G::WBUF_BYTES;
-#pragma unroll
-    for (int k = 0; k < G::NLW; ++k) {
-      const int i = tid + k * 256;
-      const int row = i / G::CH, c = i % G::CH;
-      if (i < G::GT * 32 * G::CH) *reinterpret_cast<uint4*>(dst + row * G::ROWB + ((c ^ G::swz(row)) * 16)) = wreg[k];
-    }
-  };
-
-  const int co = n0 + r;
-  const float bv = bias ? bias[co] : 0.f;
-  float ssum = 0.f, qsum = 0.f;
-  int wpar = 0;                                  // weight-ring buffer holding the current group
-
-  // prologue: slabs d0-1, d0 and weight group 0
-  slab_fetch(d0 - 1); slab_commit(d0 - 1);
-  slab_fetch(d0); slab_commit(d0);
-  slab_fetch(d0 + 1);
-  if constexpr (G::NG == 1) {                    // resident weights: straight global -> LDS, once per block
-    for (int i = tid; i < 27 * 32 * G::CH; i += 256) {
-      const int row = i / G::CH, c = i % G::CH;
-      const uint4 v = *reinterpret_cast<const uint4*>(wp + ((int64_t)(row >> 5) * Cout + n0 + (row & 31)) * CIN + c * 8);
-      *reinterpret_cast<uint4*>(wbuf + row * G::ROWB + ((c ^ G::swz(row)) * 16)) = v;
-    }
-  } else {
-    w_fetch(0); w_commit(0);
-  }
-  __syncthreads();
-  slab_commit(d0 + 1);
-  __syncthreads();
-
-  for (int d = d0; d < d1; ++d) {
-    if (d + 1 < d1) slab_fetch(d + 2);           // in flight during this depth's 27 taps
-    f32x16 acc[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
-#pragma unroll 1
-    for (int g = 0; g < G::NG; ++g) {
-      const int gn = (g + 1 == G::NG) ? 0 : g + 1;
-      if constexpr (G::NG > 1) w_fetch(gn);
-      const char* wb_ = wbuf + wpar * G::WBUF_BYTES;
-      // software pipeline: the fragments of tap tl+1 are requested before the MFMAs of tap tl are
-      // issued, so every ds_read_b128 has a full tap of matrix work (2*KS MFMAs) to land behind
-      constexpr int KS = CIN / 16;
-      bf16x8 fb[2][KS], fa[2][KS][2];
-      auto load_tap = [&](int tl, int buf) {
-        const int tap = g * G::GT + tl;
-        const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-        const char* sl = slabs + ((d + kd) % G::NSLOT) * G::SLAB_BYTES;   // depth d + kd - 1
-        const int brow = tl * 32 + r;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          const int c = 2 * s + khalf;
-          fb[buf][s] = *reinterpret_cast<const bf16x8*>(wb_ + brow * G::ROWB + ((c ^ G::swz(brow)) * 16));
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            const int vox = (wave * 2 + m + kh) * G::SW + r + kw;
-            fa[buf][s][m] = *reinterpret_cast<const bf16x8*>(sl + vox * G::ROWB + ((c ^ G::swz(vox)) * 16));
-          }
-        }
-      };
-      load_tap(0, 0);
-#pragma unroll
-      for (int tl = 0; tl < G::GT; ++tl) {
-        if (tl + 1 < G::GT) load_tap(tl + 1, (tl + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-            acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[tl & 1][s][m], fb[tl & 1][s], acc[m], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // the ring alternates buffers across the wrap-around into the next depth as well (NG is odd)
-      if constexpr (G::NG > 1) {
-        wpar ^= 1;
-        char* dst = wbuf + wpar * G::WBUF_BYTES;
-#pragma unroll
-        for (int k = 0; k < G::NLW; ++k) {
-          const int i = tid + k * 256;
-          const int row = i / G::CH, c = i % G::CH;
-          if (i < G::GT * 32 * G::CH) *reinterpret_cast<uint4*>(dst + row * G::ROWB + ((c ^ G::swz(row)) * 16)) = wreg[k];
-        }
-        __syncthreads();
-      }
-    }
-    // 3 slots: the slot of depth d-1, free since the last group barrier; 4 slots: the slot of depth d-2, free since
-    // the barrier that ended depth d-1.  The slab is committed BEFORE the output stores are issued: loads and stores
-    // share vmcnt, so waiting for the slab's registers after the stores would wait for the stores as well.
-    if (d + 1 < d1) slab_commit(d + 2);
-    // epilogue of depth d
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int h = h0 + wave * 2 + m;
-      if (h < H) {
-        const int64_t vrow = (((int64_t)n * D + d) * H + h) * W;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int w = w0 + (i & 3) + 8 * (i >> 2) + 4 * khalf;
-          if (w < W) {
-            const float o = acc[m][i] + bv;
-            y[(vrow + w) * ldy + co] = (bf16_t)o;
-            ssum += o;
-            qsum = fmaf(o, o, qsum);
-          }
-        }
-      }
-    }
-    if (d + 1 < d1) {
-      // one barrier publishes the new slab; raw (no fence): the output stores stay in flight across it
-      lds_barrier();
-    }
-  }
-  if (stats) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);            // [4][2][32]
-    const float a = ssum + __shfl_xor(ssum, 32, 64), q2 = qsum + __shfl_xor(qsum, 32, 64);
-    if (lane < 32) { red[(wave * 2 + 0) * 32 + r] = a; red[(wave * 2 + 1) * 32 + r] = q2; }
-    __syncthreads();
-    if (tid < 64) {
-      const int which = tid >> 5, c = tid & 31;
-      stats[((int64_t)blockIdx.x * 2 + which) * Cout + n0 + c] =
-          red[(0 * 2 + which) * 32 + c] + red[(1 * 2 + which) * 32 + c] + red[(2 * 2 + which) * 32 + c] + red[(3 * 2 + which) * 32 + c];
-    }
-  }
-}
-
-struct StreamCfg { int tilesH, tilesW, dsegs, dlen, nblk; };
-inline int stream_min_w() {
-  return (int)fplx_knob(FPLX_K_STREAM_MIN_W);          // tuning knob (benchmarks only)
-}
-inline bool stream_ok(int d, int h, int w, int cin, int cout) {
-  // below W = 128 (level 1) the LDS-tiled GEMM kernel is faster whenever it applies (Cout % 64 == 0)
-  const bool tile_applies = cin % 32 == 0 && cout % 64 == 0;
-  return (cin == 32 || cin == 64) && cout % 32 == 0 && h >= 16 && w >= stream_min_w() && d >= 4 &&
-         (w >= 128 || !tile_applies);
-}
-inline StreamCfg stream_cfg(int n, int d, int h, int w, int cout) {
-  StreamCfg c;
-  c.tilesH = (h + 7) / 8;
-  c.tilesW = (w + 31) / 32;
-  const int tiles = n * c.tilesH * c.tilesW * (cout / 32);
-  int ds = (1024 + tiles / 2) / tiles;
-  const int maxds = d / 8 > 0 ? d / 8 : 1;
-  if (ds > maxds) ds = maxds;
-  if (ds < 1) ds = 1;
-  c.dlen = (d + ds - 1) / ds;
-  c.dsegs = (d + c.dlen - 1) / c.dlen;
-  c.nblk = n * c.tilesH * c.tilesW * c.dsegs;
-  return c;
-}
-
-// ------------------------------------------------------------------------------------------
-// conv_fwd_tile: LDS-tiled implicit GEMM (Cin % KC == 0, Cout % 64 == 0) for every 3x3x3 layer that is not on
-// the slab-streaming kernel (levels 1-4).  Block tile = 128 voxels x NT output channels, waves 2 (M) x 2 (N).
+// conv_fwd_tile: LDS-tiled implicit GEMM (Cin % KC == 0, Cout % 64 == 0) for the 3x3x3 layers neither the march nor
+// the brick kernels take.  Block tile = MTL = 128 voxels x NT output channels, waves 2 (M) x 2 (N).
 // Per K-iteration (one tap, KC = 32 or 64 input channels) the shifted / zero-padded voxel rows (A) and the
 // weight rows (B) travel global -> registers while the previous iteration computes out of the other LDS
 // buffer, then are committed (16-byte-chunk XOR swizzle: conflict-free ds_read_b128) behind ONE barrier.
 // KC = 64 doubles the matrix work per barrier and per global-load round trip.  blockIdx.z deals the taps
 // (split-K) exactly like conv_fwd_direct.
-// MTL = 256 (8 waves, 4 (M) x 2 (N), one block per CU) keeps the per-wave work and the waves per SIMD of the 128-voxel
-// form but shares each weight tile among twice the voxels: 25 % fewer L2 -> LDS bytes per MFMA.  Measured: no gain
-// (see direct_cfg), so it is selected only by FPLX_TILE_MT=256.
-template <int NT, int KC, int MTL>
-__global__ void __launch_bounds__(MTL * 2, MTL == 128 ? 2 : 1)
+template <int NT, int KC>
+__global__ void __launch_bounds__(256, 2)
 conv_fwd_tile(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ wp, const float* __restrict__ bias,
               bf16_t* __restrict__ y, int64_t ldy, int N, int D, int H, int W, int Cin, int Cout,
               float* __restrict__ stats, float* __restrict__ partial, int tap_lo, int tap_cnt, int xcd) {
   // tap_lo / tap_cnt: the taps to run - 0 / 27, or 9 / 9 for the 2.5D levels whose 27-tap packs are zero outside the
   // middle depth plane (a third of the work, the same result)
-  constexpr int THREADS = MTL * 2, NTW = NT / 64;            // N tiles (32 wide) per wave
+  constexpr int MTL = 128, THREADS = MTL * 2, NTW = NT / 64; // voxels per block tile; N tiles (32 wide) per wave
   constexpr int ROWB = KC * 2, CH = KC / 8, RP = THREADS / CH;   // row bytes, 16-byte chunks per row, rows per pass
   constexpr int PA = MTL / RP, PB = NT / RP;                 // staging passes (chunks per thread) for A and B
   constexpr int KS = KC / 16;
@@ -2141,7 +1900,7 @@ deconv_dgrad_small(const bf16_t* __restrict__ dy, int64_t ldy, const bf16_t* __r
   }
 }
 
-struct DirectCfg { int mt, ntl, ksplit, fin_blocks, tile_nt, tile_mt; int64_t mblocks; };
+struct DirectCfg { int mt, ntl, ksplit, fin_blocks, tile_nt; int64_t mblocks; };
 
 inline DirectCfg direct_cfg(int64_t V, int cin, int cout, int taps = 27) {
   DirectCfg c;
@@ -2149,14 +1908,7 @@ inline DirectCfg direct_cfg(int64_t V, int cin, int cout, int taps = 27) {
   else { c.mt = 4; c.ntl = 1; }
   // LDS-tiled kernel (128 voxels x 128|64 channels per block) when the shape allows
   c.tile_nt = (cin % 32 == 0 && cout % 64 == 0) ? (cout % 128 == 0 ? 128 : 64) : 0;
-  c.tile_mt = 128;
-  if (c.tile_nt && cin % 64 == 0) {
-    // 256-voxel tiles: measured +-2 % at level 2 and -15 % on the 64-wide level-1 layer, so they stay a tuning knob
-    // (FPLX_TILE_MT=256) - the kernel is not simply L2-bandwidth-bound
-    const int kmt = (int)fplx_knob(FPLX_K_TILE_MT);
-    if (kmt == 256) c.tile_mt = 256;
-  }
-  c.mblocks = c.tile_nt ? (V + c.tile_mt - 1) / c.tile_mt : (V + 4 * c.mt * 32 - 1) / (4 * c.mt * 32);
+  c.mblocks = c.tile_nt ? (V + 127) / 128 : (V + 4 * c.mt * 32 - 1) / (4 * c.mt * 32);
   // small volumes (deep levels) do not fill 256 CUs: deal the 27 taps to 3 / 9 / 27 blocks - the SMALLEST split that
   // gives every CU a block, because each split adds an fp32 partial tensor to write and re-read (measured on the level-3
   // and level-4 shapes: 9 -> 3 and 27 -> 9 save 12-21 us per launch)
@@ -2168,7 +1920,6 @@ inline DirectCfg direct_cfg(int64_t V, int cin, int cout, int taps = 27) {
     else if (blocks < 256) c.ksplit = 3;
     if (c.ksplit > taps) c.ksplit = taps;
   }
-  if (c.tile_mt == 256) c.ksplit = 1;                        // chosen only where it fills the chip by itself
   {  // tuning knobs: FPLX_TILE_NT=64 forces the narrow tile, FPLX_TILE_KS forces the tap split (1/3/9/27)
     const int knt = (int)fplx_knob(FPLX_K_TILE_NT), kks = (int)fplx_knob(FPLX_K_TILE_KS);
     if (knt == 64 && c.tile_nt == 128) c.tile_nt = 64;
@@ -2203,7 +1954,6 @@ struct FwdPlan {
   size_t ws_bytes;            // split-K partials fp32 [ksplit][V][cout]; 0 without a split
   int tap_lo, tap_cnt;        // taps the tile kernel runs: 0 / 27, or 9 / 9 (mid)
   bool fits;                  // voxel indices fit 31 bits: the launchers and the plan query decline the layer otherwise
-  StreamCfg stream;           // STREAM
   DirectCfg direct;           // TILE, DIRECT
 };
 
@@ -2223,8 +1973,8 @@ static FwdPlan fwd_plan(int n, int d, int h, int w, int cin, int cout, int mid) 
     p.kernel = FPLX_KERNEL_BRICK;
     split(bricks);
   };
-  // the order: brick ahead of the march kernels where it is the faster one (fplx_brick_first), the depth marches, their
-  // predecessor (knob march = 0 | 2), brick on the layers no march kernel takes, the tile / direct implicit GEMM
+  // the order: brick ahead of the march kernels where it is the faster one (fplx_brick_first), the depth marches, brick on
+  // the layers no march kernel takes, the tile / direct implicit GEMM
   if (!mid && fplx_brick_first(n, d, h, w, cin, cout)) { brick(); return p; }
   if (fplx_march_ok(n, d, h, w, cin, cout)) {
     // (mid: the march keeps all 27 taps - its 1.0 PFLOP/s on three times the work still beats the tile kernel's short-K
@@ -2232,12 +1982,6 @@ static FwdPlan fwd_plan(int n, int d, int h, int w, int cin, int cout, int mid) 
     p.kernel = FPLX_KERNEL_MARCH;
     p.geo = fplx_march_variant(n, d, h, w, cin, cout);
     p.stats_rows = fplx_march_rows(n, d, h, w, cin, cout);
-    return p;
-  }
-  if (stream_ok(d, h, w, cin, cout)) {
-    p.kernel = FPLX_KERNEL_STREAM;
-    p.stream = stream_cfg(n, d, h, w, cout);
-    p.stats_rows = p.stream.nblk;
     return p;
   }
   if (!mid && fplx_brick_ok(n, d, h, w, cin, cout)) { brick(); return p; }
@@ -2268,7 +2012,7 @@ extern "C" size_t fplx_mfma_conv3d_fwd_ws_bytes(int n, int d, int h, int w, int 
 
 // launches fwd_plan's kernel; 0 where the operands (alignment, leading dimensions) or the form asked for are not its own.
 // slope != NULL (inference: eval-mode BatchNorm folded into the pack): PReLU in the kernel's write-out or in the split-K
-// finish; the caller has checked fplx_mfma_conv3d_act_ok (the stream / unsplit tile / direct kernels have no such form)
+// finish; the caller has checked fplx_mfma_conv3d_act_ok (the unsplit tile / direct kernels have no such form)
 static int mfma_fwd_impl(const void* x, int64_t ldx, const void* wp, const float* bias, void* y, int64_t ldy, int n, int d,
                          int h, int w, int cin, int cout, float* stats, void* ws, size_t ws_bytes, int mid,
                          hipStream_t st, const float* slope = nullptr) {
@@ -2294,24 +2038,14 @@ static int mfma_fwd_impl(const void* x, int64_t ldx, const void* wp, const float
     }
     case FPLX_KERNEL_MARCH:
       return fplx_march_conv3d_fwd_act(x, ldx, wp, bias, y, ldy, n, d, h, w, cin, cout, stats, st, nullptr, nullptr, mid, slope, 0);
-    case FPLX_KERNEL_STREAM: {
-      if (slope) return 0;
-      const StreamCfg& sc = p.stream;
-      const auto k = cin == 32 ? conv_fwd_stream<32> : conv_fwd_stream<64>;
-      fplx_launch(k, dim3(sc.nblk, cout / 32), 256, cin == 32 ? StreamGeo<32>::LDS : StreamGeo<64>::LDS, st, (const bf16_t*)x, ldx,
-                  (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cout, stats, sc.tilesH, sc.tilesW, sc.dsegs, sc.dlen);
-      int rc0 = fplx_check_launch("mfma_conv3d_fwd_stream");
-      return rc0 < 0 ? rc0 : 1;
-    }
     case FPLX_KERNEL_TILE: {
       if (slope && ks <= 1) return 0;                          // no activation form of the unsplit tile kernel
       const DirectCfg& c = p.direct;
       const bool k64 = cin % 64 == 0;
-      const int kc = (c.tile_mt == 256 || k64) ? 64 : 32;
-      const auto k = c.tile_mt == 256 ? (c.tile_nt == 128 ? conv_fwd_tile<128, 64, 256> : conv_fwd_tile<64, 64, 256>)
-                     : c.tile_nt == 128 ? (k64 ? conv_fwd_tile<128, 64, 128> : conv_fwd_tile<128, 32, 128>)
-                                        : (k64 ? conv_fwd_tile<64, 64, 128> : conv_fwd_tile<64, 32, 128>);
-      fplx_launch(k, dim3((unsigned)c.mblocks, cout / c.tile_nt, ks), c.tile_mt * 2, (size_t)2 * (c.tile_mt + c.tile_nt) * kc * 2, st,
+      const int kc = k64 ? 64 : 32;
+      const auto k = c.tile_nt == 128 ? (k64 ? conv_fwd_tile<128, 64> : conv_fwd_tile<128, 32>)
+                                      : (k64 ? conv_fwd_tile<64, 64> : conv_fwd_tile<64, 32>);
+      fplx_launch(k, dim3((unsigned)c.mblocks, cout / c.tile_nt, ks), 256, (size_t)2 * (128 + c.tile_nt) * kc * 2, st,
                   (const bf16_t*)x, ldx, (const bf16_t*)wp, bias, (bf16_t*)y, ldy, n, d, h, w, cin, cout, stats, partial, p.tap_lo,
                   p.tap_cnt, fplx_xcd_on());
       if (ks > 1) splitk_finish_k<<<c.fin_blocks, 256, 0, st>>>(partial, ks, V, cout, bias, (bf16_t*)y, ldy, stats, slope);

@@ -70,15 +70,6 @@ class Engine(object):
         # forward / backward above that site's activation has no reader left and is neither allocated nor written
         self.use_outconv_wgrad_bn = _lib.host_knob("outconv_wgrad_bn") != 0
         self._fold_cache = {}              # (act dtype, domain) -> {site key: (folded forward pack, folded bias)}
-        # TIMING PROBE ONLY (tools/step_ab.py "@defer_probe=1"): the decoder's weight gradients of a step are
-        # not launched in backward but beside the NEXT step's forward - their results are discarded by that step's gradient
-        # zeroing, so training is wrong; what is measured is the step time a pipelined optimiser step could reach
-        self.defer_probe = False
-        self._deferred = []
-        # block_joins: the main stream waits for the weight-gradient stream at every block boundary of backward.
-        # None = decide per network (see backward()); a bisection tool may set it (round 2's tools/race25.py, git history).
-        self.block_joins = None
-        self.debug_tap = None              # callable(name, tensor) on intermediate gradients of backward (bisection tools)
 
     # ------------------------------------------------------------------ helpers
     def _workspace(self, nbytes, dev):
@@ -186,12 +177,6 @@ class Engine(object):
         packs["out_conv"] = (wf, wb)
         return packs
 
-    def default_block_joins(self):
-        """No joins at block boundaries: backward's main stream never waits for the weight-gradient stream until the end.
-        (Round 1 needed them for networks with 2D levels; the cause was a store-data hazard inside the march kernels'
-        inline-asm 16-byte stores, fixed there - DESIGN section 7, profiles/r02_race25_hazard_location.txt.)"""
-        return False
-
     _tuning_epoch = -1
 
     def _pack_key(self, adt):
@@ -286,20 +271,6 @@ class Engine(object):
             packs = self._pack_cache[1]
         if train:
             self._fold_cache = {}                        # the running statistics are about to change
-        deferred_join = None
-        if train and self._deferred and self._side is not None:
-            # timing probe (defer_probe): the previous step's decoder weight gradients run beside this forward
-            main_ = torch.cuda.current_stream()
-            ev = torch.cuda.Event()
-            ev.record(main_)
-            self._side.wait_event(ev)
-            with torch.cuda.stream(self._side):
-                for fn_, _ in self._deferred:
-                    fn_()
-                deferred_join = torch.cuda.Event()
-                deferred_join.record(self._side)
-            self._deferred_keep = self._deferred
-            self._deferred = []
         fuse = self.use_eval_fusion and not train and not keep and adt == torch.bfloat16
         # the last site's BatchNorm + PReLU inside the out_conv kernel (not where that site runs the folded inference form)
         oc_fuse = (self.use_outconv_fusion and not fuse and mc == 1 and adt == torch.bfloat16 and
@@ -492,9 +463,6 @@ class Engine(object):
                            ops.planar_strides(ncls, D, H, W), F32, dims[0], ft[0], ncls, (1, 3, 3), None)
         sv.oc_fused = oc_fuse
         sv.oc_wg = oc_wg
-        if deferred_join is not None:
-            torch.cuda.current_stream().wait_event(deferred_join)
-            self._deferred_keep = None
         return logits, (sv if keep else None)
 
     # ------------------------------------------------------------------ backward
@@ -547,18 +515,9 @@ class Engine(object):
             self._side = torch.cuda.Stream(device=dev)
         side = self._side if side_on else None
         keep = []                          # tensors the side stream still reads: kept alive until the join
-        block_joins = self.block_joins
-        tap = self.debug_tap
-        if block_joins is None:
-            block_joins = self.default_block_joins()
         ws_w = self.ws_side if side_on else ws
 
-        decoder_phase = [True]
-
         def on_side(fn, *tensors):
-            if self.defer_probe and side_on and decoder_phase[0]:
-                self._deferred.append((fn, tensors))
-                return
             if not side_on:
                 fn()
                 return
@@ -597,9 +556,8 @@ class Engine(object):
                                              gv["out_conv.bias"], dims[0], ft[0], ncls, (1, 3, 3), ws_w), dlogits)
 
         def ready(last_name):
-            """block boundary: the gradients of flat elements [0, end of last_name) have been enqueued"""
-            if block_joins:
-                join_side()
+            """block boundary: the gradients of flat elements [0, end of last_name) have been enqueued.  Without a callback the
+            main stream never waits for the weight-gradient stream here, only at the end of backward."""
             if on_ready is None:
                 return
             o, n, _ = net._layout[last_name]
@@ -609,7 +567,7 @@ class Engine(object):
             pending = getattr(getattr(on_ready, "__self__", None), "pending", None)
             if pending is not None and not pending(end):
                 return
-            if side_on and pending is not None and not block_joins:
+            if side_on and pending is not None:
                 # the bucket's weight gradients were produced on the side stream, its BN / bias gradients on this
                 # one: launch the collective FROM the side stream once that has caught up with this stream's
                 # position - the communication stream then depends on both and the data-gradient chain never waits
@@ -644,7 +602,7 @@ class Engine(object):
                                          dims[l], c, ncls)
             else:
                 # (the stem site: no data gradient, so dy's only consumer is the weight gradient - which forms it itself)
-                stem_fused = (self.use_stem_wgrad_bn and not want_dx and tap is None and sv.train and x_dt == F32 and p == 0.0 and
+                stem_fused = (self.use_stem_wgrad_bn and not want_dx and sv.train and x_dt == F32 and p == 0.0 and
                               gv[key + ".weight"].dim() == 5 and adt == torch.bfloat16 and not isinstance(xin, tuple) and
                               ops.ld_of(d_out) % 8 == 0 and d_out.data_ptr() % 16 == 0 and ops.stem_wgrad_bn_ok(dims[l], cin, c))
                 ops.bn_act_bwd(y, d_out, d_out, bnbuf, net.get_param(relukey + ".weight"), p, sv.seed, sid, c, sv.train,
@@ -658,8 +616,6 @@ class Engine(object):
                     else:
                         on_side(fn, d_out, xin, y, coef)
                     return
-            if tap is not None:
-                tap(key + ".dy", d_out)
             # conv bias followed by train-mode BatchNorm: d/d bias == sum of dy == 0 exactly
             db = None if sv.train else gv[key + ".bias"]
             gw = gv[key + ".weight"]
@@ -667,9 +623,6 @@ class Engine(object):
             if isinstance(xin, tuple):                 # cat([skip, up]) as two tensors (train-mode BN only: db is None)
                 if want_dx:
                     ops.conv3d_dgrad_split2(d_out, packs[key][1], dx_view[0], dx_view[1], dims[l], cin, c, two_d)
-                    if tap is not None:
-                        tap(key + ".dx0", dx_view[0])
-                        tap(key + ".dx1", dx_view[1])
                 on_side(lambda: ops.conv3d_wgrad_cat2(xin[0], xin[1], d_out, gw, dims[l], cin, c, ws_w, two_d),
                         d_out, xin[0], xin[1])
                 return
@@ -691,8 +644,6 @@ class Engine(object):
                 ops.conv3d_fwd(d_out, ops.cl_strides(*dims[l][1:], c), a_dt, packs[key][1], None, dx_view,
                                ops.cl_strides(*dims[l][1:], ops.ld_of(dx_view)), a_dt, dims[l], c, cin, (3, 3, 3), None,
                                mid=two_d)
-                if tap is not None:
-                    tap(key + ".dx", dx_view)
             # the weight gradient is enqueued BEHIND the data gradient: the side stream's event then follows the data-gradient
             # kernel, so the two matrix kernels of a site do not start together and split the chip - the weight gradient runs
             # beside the next site's BatchNorm passes (memory-bound) instead (measured -0.4 % on the step)
@@ -740,8 +691,6 @@ class Engine(object):
                 d_cur = empty(vox[l + 1], ft[l + 1])
                 ops.conv3d_fwd(d_low, lows, a_dt, packs[name][1], None, d_cur, highs, a_dt, dims[l + 1], ft[l], ft[l + 1],
                                (1, 1, 1), None)
-                if tap is not None:
-                    tap(name + ".dx", d_cur)
                 continue
             def deconv_wgrad(xin=xin, d_up=d_up, name=name, l=l, d_cat=d_cat):
                 on_side(lambda: ops.deconv2_wgrad(xin, d_up, gv[name + ".weight"], gv[name + ".bias"], dims[l + 1], ft[l + 1],
@@ -750,10 +699,7 @@ class Engine(object):
             ops.deconv2_dgrad(d_up, packs[name][1], d_cur, dims[l + 1], ft[l + 1], ft[l], pds[l])
             deconv_wgrad()                         # behind the data gradient, like the out_conv pair above
             ready(name + ".bias")
-            if tap is not None:
-                tap(name + ".dx", d_cur)
         # ---- encoder, block4 .. block0
-        decoder_phase[0] = False
         d_pool = block_bwd(4, d_cur, True)                            # grad w.r.t. pooled3 [V_4, ft_3]
         ready("block4.conv.relu_1.weight")
         for i in range(3, -1, -1):

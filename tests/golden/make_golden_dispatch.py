@@ -7,6 +7,13 @@ fixture pins what the dispatch answered before it was rewritten as one plan per 
 knobs in full and, for every other knob setting, only the cells that differ (expand() rebuilds every row).  Every value is an integer a host
 query of the public ABI (include/fplx.h) returns - no GPU is needed.  tests/test_host_cpu.py replays GRID under every
 setting of KNOBS against the built library and requires equality of every integer.
+
+The settings march=0 and brick=0,march=0 were recorded again from a build of 348c0c2, the commit before the slab-stream forward
+(plan kernel 3) was removed, with that kernel's minimum-width knob of that commit at 1 << 30 besides: it then accepts no layer and
+the layers fall through to the next entry of fwd_plan's order, which is the plan without that kernel.  Only grid points whose
+plan kernel was 3 changed (27 and 33 points; 159 and 177 cells differ in all), and under march=0 six of the 159 are
+conv2d_stats_rows at other points (volumes 0, 5 and 10 at 64 -> 64 | 128): the 3D plan there is the brick kernel, which has no
+Conv2d form, so the 2.5D plan had been kernel 3 too.  Every other line of the fixture is the first recording's.
 """
 import ctypes
 import json
@@ -20,7 +27,7 @@ VOLUMES = [(2, 80, 160, 160), (2, 40, 80, 80), (2, 20, 40, 40), (2, 10, 20, 20),
 CHANNELS = [(16, 32), (32, 32), (64, 32), (32, 64), (64, 64), (128, 64), (64, 128), (128, 128), (256, 128), (256, 256),
             (256, 512), (512, 512), (512, 256), (48, 48), (96, 64), (32, 96)]
 # each applied over the shipped defaults
-KNOBS = [{}, {"brick": 0}, {"brick": 3}, {"march": 0}, {"march": 2}, {"brick": 0, "march": 0}, {"mid_tile": 0}, {"wg_roll": 0},
+KNOBS = [{}, {"brick": 0}, {"brick": 3}, {"march": 0}, {"brick": 0, "march": 0}, {"mid_tile": 0}, {"wg_roll": 0},
          {"wg_roll2d": 0}, {"wg_vox": 0}, {"wg_vox": 2}, {"tile_ks": 9}, {"rows_small_div": 64}, {"brick_geo": 1, "brick_ksplit": 2},
          {"march128": 0}, {"march32_v2": 0}, {"march64_fw": 16}]
 STEM_CIN, OUT_CLASSES = 1, 2            # the stem reads in_chns = 1, the out_conv writes two classes

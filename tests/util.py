@@ -19,8 +19,8 @@ def max_rel(a, b):
 
 
 def plan_kernel(n, d, h, w, cin, cout, k=(3, 3, 3), x_dt=1, y_dt=1, full=False):
-    """fplx_conv3d_plan_query: the kernel family (FPLX_KERNEL_*: 0 generic, 1 direct, 2 tile, 3 stream, 4 march, 5 brick,
-    6 stem, 7 out_conv) fplx_conv3d_fwd dispatches a layer to; full=True -> (kernel, geometry, ksplit, stats_rows)"""
+    """fplx_conv3d_plan_query: the kernel family (FPLX_KERNEL_*: 0 generic, 1 direct, 2 tile, 4 march, 5 brick, 6 stem,
+    7 out_conv; 3 is reserved) fplx_conv3d_fwd dispatches a layer to; full=True -> (kernel, geometry, ksplit, stats_rows)"""
     import ctypes
     from fplx import _lib
     kern, g, ks, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
