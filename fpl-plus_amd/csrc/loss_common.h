@@ -3,6 +3,7 @@
 // voxel, the kernel that reduces the partial rows (seg_loss_sums_k: an anonymous-namespace kernel, so each of the two files compiles
 // its own copy of it into the library), the first family's part of the one-thread finalize and the first family's gradient
 // terms of the backward voxel loop.  The rest of the voxel loops stays in their own files (loss_ext.hip says why).
+// ssl.hip (the semi-supervised passes) takes the limits, loss_rows / grid1 and softmax_argmax from here and nothing else.
 #pragma once
 #include "common.h"
 

@@ -22,7 +22,9 @@ from .train import TrainStep                                       # noqa: E402
 from .config import parse_config, synchronize_config               # noqa: E402
 from .dataset import NiftyDataset                                  # noqa: E402
 from .postprocess import PostProcess, PostKeepLargestComponent, PostProcessDict, get_largest_k_components  # noqa: E402
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess                        # noqa: E402
+from .ssl import (SSLSegAgent, SSLEntropyMinimization, SSLMeanTeacher, SSLUncertaintyAwareMeanTeacher,   # noqa: E402
+                  SSLMethodDict, EntropyLoss, consistency_loss, ema_update, get_rampup_ratio)
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl                   # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -30,4 +32,6 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "FusedRMSprop", "FusedRprop", "get_optimizer", "get_lr_scheduler", "TrainStep",
            "parse_config", "synchronize_config", "filter", "ops", "ddp", "transform", "nifti", "evaluation", "NiftyDataset",
            "postprocess", "SegLossDictAll", "FocalDiceLoss", "NoiseRobustDiceLoss", "ExpLogLoss", "GeneralizedCELoss", "MAELoss",
-           "MSELoss", "SLSRLoss", "DeepSuperviseLoss", "UNet2D5", "UNet3D", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components"]
+           "MSELoss", "SLSRLoss", "DeepSuperviseLoss", "UNet2D5", "UNet3D", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components",
+           "ssl", "SSLSegAgent", "SSLEntropyMinimization", "SSLMeanTeacher", "SSLUncertaintyAwareMeanTeacher", "SSLMethodDict",
+           "EntropyLoss", "consistency_loss", "ema_update", "get_rampup_ratio"]

@@ -1097,3 +1097,89 @@ def keep_largest_component(seg, mode=1):
          stream())
     _cc_check(ws)
     return out
+
+
+# ---- semi-supervised learning (include/fplx.h, "semi-supervised learning"; csrc/ssl.hip)
+def _ssl_f32(*ts):
+    require_gpu(*ts)
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("fplx ssl: tensors must be contiguous fp32")
+
+
+def ssl_perturb(x, noise=None, reps=1, sigma=0.1, clip=0.2, seed=0, stream_id=0, out=None):
+    """-> y [reps, *x.shape] = x + clamp(sigma z, -clip, clip) per repetition (ssl_mt.py:79, ssl_uamt.py:83-85); z = `noise`
+    ([reps, *x.shape] fp32, torch's CPU result bit for bit) or, with noise None, drawn on the device from (seed, stream_id)"""
+    _ssl_f32(x, noise, out)
+    n = x.numel()
+    if noise is not None and noise.numel() != reps * n:
+        raise ValueError("fplx ssl_perturb: noise has {0:} elements for {1:} x {2:}".format(noise.numel(), reps, n))
+    out = torch.empty((reps,) + tuple(x.shape), dtype=torch.float32, device=x.device) if out is None else out
+    if out.numel() != reps * n:
+        raise ValueError("fplx ssl_perturb: out has {0:} elements for {1:} x {2:}".format(out.numel(), reps, n))
+    call("fplx_ssl_perturb", ptr(x), ptr(noise), ptr(out), n, int(reps), float(sigma), float(clip),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, stream())
+    return out
+
+
+def ssl_part(logits, k):
+    """the fp32 partial-row workspace of a consistency (k = 2) or entropy (k = 1) forward over `logits`"""
+    n, _, v = _ncv(logits)
+    return torch.empty((n, loss_rows(v), k), dtype=torch.float32, device=logits.device)
+
+
+def ssl_consistency_fwd(student, teacher, mc=None, thr=0.0, softmax=True, part=None, out=None, mask=None):
+    """student, teacher [N, C, ...]; mc [T, N, C, ...] or None (MeanTeacher) -> (out double [4]: masked sum of squares, kept
+    voxels, loss, 0; mask uint8 [N, ...] or None)"""
+    _ssl_f32(student, teacher, mc)
+    n, c, v = _ncv(student)
+    if teacher.shape != student.shape:
+        raise ValueError("fplx ssl: teacher {0:} and student {1:} differ in shape".format(tuple(teacher.shape), tuple(student.shape)))
+    t = 0 if mc is None else int(mc.shape[0])
+    if mc is not None and tuple(mc.shape[1:]) != tuple(student.shape):
+        raise ValueError("fplx ssl: mc must be [T] + the student's shape, got {0:}".format(tuple(mc.shape)))
+    dev = student.device
+    part = ssl_part(student, 2) if part is None else part
+    out = torch.empty(4, dtype=torch.float64, device=dev) if out is None else out
+    if t > 0 and mask is None:
+        mask = torch.empty((n,) + tuple(student.shape[2:]), dtype=torch.uint8, device=dev)
+    call("fplx_ssl_consistency_fwd", ptr(student), ptr(teacher), ptr(mc), t, n, c, v, float(thr), 1 if softmax else 0,
+         ptr(mask) if t > 0 else 0, ptr(part), ptr(out), stream())
+    return out, (mask if t > 0 else None)
+
+
+def ssl_consistency_bwd(student, teacher, mask, out, gscale, t, softmax=True, dstudent=None):
+    """-> dstudent = gscale[0] dLoss/dstudent of the forward that wrote `out` and `mask` (t: its number of MC passes)"""
+    _ssl_f32(student, teacher, gscale)
+    n, c, v = _ncv(student)
+    dstudent = torch.empty_like(student) if dstudent is None else dstudent
+    call("fplx_ssl_consistency_bwd", ptr(student), ptr(teacher), ptr(mask), ptr(out), ptr(gscale), n, c, v, int(t),
+         1 if softmax else 0, ptr(dstudent), stream())
+    return dstudent
+
+
+def ssl_entropy_fwd(logits, softmax=True, part=None, out=None):
+    """EntropyLoss (loss/seg/ssl.py:32-44) -> out double [4]: sum of -sum_c p' ln p', N V, loss, 0"""
+    _ssl_f32(logits)
+    n, c, v = _ncv(logits)
+    part = ssl_part(logits, 1) if part is None else part
+    out = torch.empty(4, dtype=torch.float64, device=logits.device) if out is None else out
+    call("fplx_ssl_entropy_fwd", ptr(logits), n, c, v, 1 if softmax else 0, ptr(part), ptr(out), stream())
+    return out
+
+
+def ssl_entropy_bwd(logits, gscale, softmax=True, dlogits=None):
+    _ssl_f32(logits, gscale)
+    n, c, v = _ncv(logits)
+    dlogits = torch.empty_like(logits) if dlogits is None else dlogits
+    call("fplx_ssl_entropy_bwd", ptr(logits), ptr(gscale), n, c, v, 1 if softmax else 0, ptr(dlogits), stream())
+    return dlogits
+
+
+def ema_step(ema, p, alpha):
+    """ema = alpha ema + (1 - alpha) p in place over two flat fp32 buffers of the same length (ssl_mt.py:112-113)"""
+    _ssl_f32(ema, p)
+    if ema.numel() != p.numel():
+        raise ValueError("fplx ema_step: {0:} and {1:} elements".format(ema.numel(), p.numel()))
+    call("fplx_ema_step", ptr(ema), ptr(p), ema.numel(), float(alpha), stream())
+    return ema

@@ -715,6 +715,50 @@ int fplx_add_noise_f64(const float* x, const double* noise, float* y, int64_t n,
 int fplx_add_noise_philox(const float* x, float* y, int64_t n, uint64_t seed, uint32_t stream_id, double mean, double sigma,
                           double* out_uniforms, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ semi-supervised learning (csrc/ssl.hip)
+ * What the reference's second entry point adds to an iteration (PyMIC/pymic/net_run_ssl/ssl_em.py, ssl_mt.py, ssl_uamt.py),
+ * each as one pass.  Logits fp32 [N][C][V] contiguous, 2 <= C <= 8, 1 <= N <= 65535, any V >= 1.  Reductions as in the loss
+ * families: `part` fp32 [N][fplx_loss_rows(V)][K] (the block partials; K = 2 for the consistency, 1 for the entropy), the rows
+ * summed in double in a fixed order - no floating-point atomics, two runs give the same bits.  A lane takes four voxels with
+ * 16-byte loads where every tensor base is 16-byte aligned and V is a multiple of 4, else one voxel; the flat passes take
+ * n / 4 quads and a scalar tail.  FPLX_E_BADSHAPE / FPLX_E_NULL before any launch.
+ *  ssl_perturb: y[r][i] = x[i] + clamp(sigma z[r][i], -clip, clip), r < reps (1..64): `x1 + torch.clamp(torch.randn_like(x1) *
+ *             0.1, -0.2, 0.2)` of ssl_mt.py:79 and, with reps = 2, ssl_uamt.py:83-85.  Three fp32 operations, none contracted:
+ *             with z = the caller's fp32 noise[reps][n] the result is torch's on the CPU bit for bit.  noise NULL: z is drawn on the
+ *             device - element i of repetition r takes words 2 (i & 1), 2 (i & 1) + 1 of Philox4x32-10 with counter
+ *             (i >> 1, r, stream_id, i >> 33) and key (seed low, seed high), u = (word + 1) / 2^32, z = float32(sqrt(-2 ln u1)
+ *             cos(2 pi u2)) formed in fp64 (the Box-Muller of add_noise_philox).
+ *  ssl_consistency_fwd: student, teacher [N][C][V]; mc [T][N][C][V] or NULL with t = 0; t even, at most 16.  softmax = 1:
+ *             softmax over C of all three inputs; 0: they are probabilities.  t = 0 (MeanTeacher) keeps every voxel; t > 0 (UAMT,
+ *             ssl_uamt.py:91-99): m_c = (sum_t softmax(mc_t)_c) / T, unc = -sum_c m_c log(m_c + 1e-6), kept iff unc < thr,
+ *             the flag written to mask uint8 [N][V] (needed iff t > 0).
+ *             out double [4]: sum over kept voxels and classes of (p_c - q_c)^2; number of kept voxels; the loss; 0.
+ *             loss = out0 / (N C V) for t = 0 (torch.nn.MSELoss(), ssl_mt.py:100), out0 / (2 out1 + 1e-16) for t > 0
+ *             (ssl_uamt.py:100 - the 2 is the reference's literal, not C).
+ *  ssl_consistency_bwd: e_c = 2 (p_c - q_c) k / D, k the kept flag (1 with t = 0), D the denominator above (read from out[1]
+ *             on the device when t > 0; out may be NULL with t = 0); dstudent_c = gscale[0] p_c (e_c - sum_j p_j e_j), with
+ *             softmax = 0 gscale[0] e_c.  gscale: device fp32 scalar.  The teacher receives no gradient.
+ *  ssl_entropy_fwd / _bwd: EntropyLoss (loss/seg/ssl.py:32-44): p' = 0.999 p + 5e-4, H = -sum_c p'_c ln p'_c / ln C, loss = mean
+ *             of H over N V.  out double [4]: sum over the voxels of -sum_c p'_c ln p'_c; N V; the loss; 0.  Backward:
+ *             dL/dp_c = -0.999 (ln p'_c + 1) / (ln C N V), then the softmax Jacobian (softmax = 0: as it is), times gscale[0].
+ *             (Not the first family's entropy term: that one is log2 with + 1e-10, agent_seg.py:352-354.)
+ *  ema_step:  ema = alpha ema + (1 - alpha) p over a flat fp32 segment, 0 <= alpha <= 1 (`ema_param.data.mul_(alpha).add_(1 -
+ *             alpha, param.data)`, ssl_mt.py:112-113, for all parameters in one launch); 1 - alpha is formed in double on the
+ *             host and rounded once, the element is fma(alpha, ema, (1 - alpha) p). */
+int fplx_ssl_perturb(const float* x, const float* noise, float* y, int64_t n, int reps, float sigma, float clip, uint64_t seed,
+                     uint32_t stream_id, fplx_stream_t stream);
+int fplx_ssl_consistency_fwd(const float* student, const float* teacher, const float* mc, int t, int n, int c,
+                             int64_t voxels_per_sample, float thr, int softmax, uint8_t* mask, float* part, double* out,
+                             fplx_stream_t stream);
+int fplx_ssl_consistency_bwd(const float* student, const float* teacher, const uint8_t* mask, const double* out,
+                             const float* gscale, int n, int c, int64_t voxels_per_sample, int t, int softmax, float* dstudent,
+                             fplx_stream_t stream);
+int fplx_ssl_entropy_fwd(const float* logits, int n, int c, int64_t voxels_per_sample, int softmax, float* part, double* out,
+                         fplx_stream_t stream);
+int fplx_ssl_entropy_bwd(const float* logits, const float* gscale, int n, int c, int64_t voxels_per_sample, int softmax,
+                         float* dlogits, fplx_stream_t stream);
+int fplx_ema_step(float* ema, const float* p, int64_t n, float alpha, fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
