@@ -24,7 +24,9 @@ from .dataset import NiftyDataset                                  # noqa: E402
 from .postprocess import PostProcess, PostKeepLargestComponent, PostProcessDict, get_largest_k_components  # noqa: E402
 from .ssl import (SSLSegAgent, SSLEntropyMinimization, SSLMeanTeacher, SSLUncertaintyAwareMeanTeacher,   # noqa: E402
                   SSLMethodDict, EntropyLoss, consistency_loss, ema_update, get_rampup_ratio)
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl                   # noqa: E402
+from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMumfordShah, WSLGatedCRF, WSLUSTM,  # noqa: E402
+                  WSLMethodDict, TotalVariationLoss, MumfordShahLoss, GatedCRFLoss)
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl              # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -34,4 +36,6 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "postprocess", "SegLossDictAll", "FocalDiceLoss", "NoiseRobustDiceLoss", "ExpLogLoss", "GeneralizedCELoss", "MAELoss",
            "MSELoss", "SLSRLoss", "DeepSuperviseLoss", "UNet2D5", "UNet3D", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components",
            "ssl", "SSLSegAgent", "SSLEntropyMinimization", "SSLMeanTeacher", "SSLUncertaintyAwareMeanTeacher", "SSLMethodDict",
-           "EntropyLoss", "consistency_loss", "ema_update", "get_rampup_ratio"]
+           "EntropyLoss", "consistency_loss", "ema_update", "get_rampup_ratio",
+           "wsl", "WSLSegAgent", "WSLEntropyMinimization", "WSLTotalVariation", "WSLMumfordShah", "WSLGatedCRF", "WSLUSTM",
+           "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss"]

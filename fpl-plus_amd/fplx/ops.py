@@ -1183,3 +1183,101 @@ def ema_step(ema, p, alpha):
         raise ValueError("fplx ema_step: {0:} and {1:} elements".format(ema.numel(), p.numel()))
     call("fplx_ema_step", ptr(ema), ptr(p), ema.numel(), float(alpha), stream())
     return ema
+
+
+# ---- weakly-supervised learning (include/fplx.h, "weakly-supervised learning"; csrc/wsl.hip)
+_CRF_TILE = 16
+
+
+def _wsl_dims(logits, image=None):
+    """logits [N, C, D, H, W] (and the image [N, Ci, D, H, W] of the same spatial shape) -> (n, c, ci, d, h, w)"""
+    if logits.dim() != 5:
+        raise ValueError("fplx wsl: logits must be [N, C, D, H, W], got {0:}D".format(logits.dim()))
+    n, c, d, h, w = (int(s) for s in logits.shape)
+    ci = 0
+    if image is not None:
+        if image.dim() != 5 or image.shape[0] != n or tuple(image.shape[2:]) != (d, h, w):
+            raise ValueError("fplx wsl: image {0:} does not match logits {1:}".format(tuple(image.shape), tuple(logits.shape)))
+        ci = int(image.shape[1])
+    return n, c, ci, d, h, w
+
+
+def wsl_gatedcrf_fwd(logits, image, desc, radius, softmax=True, kp=None, part=None, out=None):
+    """GatedCRFLoss.forward (loss/seg/gatedcrf.py:18-110, Potts, no masks) over the slices of logits [N, C, D, H, W] and image
+    [N, Ci, D, H, W]; desc: [(weight, sigma_xy, sigma_rgb)] with 0 for an absent modality -> (out double [4]: the sum, 0, the
+    loss, N D H W; kp fp32, the shape of the logits)"""
+    _ssl_f32(logits, image, kp, part)
+    n, c, ci, d, h, w = _wsl_dims(logits, image)
+    flat = [float(x) for row in desc for x in row]
+    if len(flat) != 3 * len(desc):
+        raise ValueError("fplx wsl: a kernel descriptor is (weight, sigma_xy, sigma_rgb)")
+    arr = (ctypes.c_float * max(len(flat), 1))(*flat)
+    dev = logits.device
+    kp = torch.empty_like(logits) if kp is None else kp
+    rows = n * d * ((h + _CRF_TILE - 1) // _CRF_TILE) * ((w + _CRF_TILE - 1) // _CRF_TILE)
+    part = torch.empty(rows, dtype=torch.float32, device=dev) if part is None else part
+    if part.numel() < rows:
+        raise ValueError("fplx wsl: part has {0:} elements, {1:} needed".format(part.numel(), rows))
+    out = torch.empty(4, dtype=torch.float64, device=dev) if out is None else out
+    call("fplx_wsl_gatedcrf_fwd", ptr(logits), ptr(image), n, c, ci, d, h, w, ctypes.cast(arr, ctypes.c_void_p), len(desc),
+         int(radius), 1 if softmax else 0, ptr(kp), ptr(part), ptr(out), stream())
+    return out, kp
+
+
+def wsl_gatedcrf_bwd(logits, kp, gscale, softmax=True, dlogits=None):
+    """-> dlogits = gscale[0] dLoss/dlogits of the forward that wrote `kp`"""
+    _ssl_f32(logits, kp, gscale, dlogits)
+    n, c, _, d, h, w = _wsl_dims(logits)
+    dlogits = torch.empty_like(logits) if dlogits is None else dlogits
+    call("fplx_wsl_gatedcrf_bwd", ptr(logits), ptr(kp), ptr(gscale), n, c, d, h, w, 1 if softmax else 0, ptr(dlogits), stream())
+    return dlogits
+
+
+def wsl_tv_fwd(logits, softmax=True, count=None, ws=None, part=None, out=None):
+    """TotalVariationLoss.forward (loss/seg/ssl.py:68-86) for logits [N, C, D, H, W] -> (out double [4]: sum of contour, 0,
+    the loss, N C D H W; count int32, the shape of the logits)"""
+    _ssl_f32(logits, part)
+    n, c, _, d, h, w = _wsl_dims(logits)
+    dev = logits.device
+    e = logits.numel()
+    count = torch.empty(logits.shape, dtype=torch.int32, device=dev) if count is None else count
+    ws = torch.empty(3 * e, dtype=torch.int32, device=dev) if ws is None else ws
+    part = torch.empty(n * c * loss_rows(d * h * w), dtype=torch.float32, device=dev) if part is None else part
+    out = torch.empty(4, dtype=torch.float64, device=dev) if out is None else out
+    require_gpu(count, ws)
+    if count.dtype != torch.int32 or count.numel() != e or not count.is_contiguous():
+        raise ValueError("fplx wsl: count must be contiguous int32 of the logits' shape")
+    call("fplx_wsl_tv_fwd", ptr(logits), n, c, d, h, w, 1 if softmax else 0, ptr(count), ptr(ws), ws.numel() * ws.element_size(),
+         ptr(part), ptr(out), stream())
+    return out, count
+
+
+def wsl_tv_bwd(logits, count, gscale, softmax=True, dlogits=None):
+    _ssl_f32(logits, gscale, dlogits)
+    n, c, _, d, h, w = _wsl_dims(logits)
+    dlogits = torch.empty_like(logits) if dlogits is None else dlogits
+    call("fplx_wsl_tv_bwd", ptr(logits), ptr(count), ptr(gscale), n, c, d, h, w, 1 if softmax else 0, ptr(dlogits), stream())
+    return dlogits
+
+
+def wsl_mumford_shah_fwd(logits, image, penalty=1, lam=1.0, softmax=True, cen=None, part=None, out=None):
+    """MumfordShahLoss.forward (loss/seg/mumford_shah.py:62-95) -> (out double [4]: the level-set sum, the gradient sum, the
+    loss, N C D H W; cen fp32 [N, D, Ci, C], the per-slice centroids)"""
+    _ssl_f32(logits, image, cen, part)
+    n, c, ci, d, h, w = _wsl_dims(logits, image)
+    dev = logits.device
+    cen = torch.empty((n, d, ci, c), dtype=torch.float32, device=dev) if cen is None else cen
+    part = torch.empty(n * d * loss_rows(h * w) * c * (1 + ci), dtype=torch.float32, device=dev) if part is None else part
+    out = torch.empty(4, dtype=torch.float64, device=dev) if out is None else out
+    call("fplx_wsl_mumford_shah_fwd", ptr(logits), ptr(image), n, c, ci, d, h, w, int(penalty), float(lam), 1 if softmax else 0,
+         ptr(cen), ptr(part), ptr(out), stream())
+    return out, cen
+
+
+def wsl_mumford_shah_bwd(logits, image, cen, gscale, penalty=1, lam=1.0, softmax=True, dlogits=None):
+    _ssl_f32(logits, image, cen, gscale, dlogits)
+    n, c, ci, d, h, w = _wsl_dims(logits, image)
+    dlogits = torch.empty_like(logits) if dlogits is None else dlogits
+    call("fplx_wsl_mumford_shah_bwd", ptr(logits), ptr(image), ptr(cen), ptr(gscale), n, c, ci, d, h, w, int(penalty), float(lam),
+         1 if softmax else 0, ptr(dlogits), stream())
+    return dlogits

@@ -759,6 +759,53 @@ int fplx_ssl_entropy_bwd(const float* logits, const float* gscale, int n, int c,
                          float* dlogits, fplx_stream_t stream);
 int fplx_ema_step(float* ema, const float* p, int64_t n, float alpha, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ weakly-supervised learning (csrc/wsl.hip)
+ * The regularisers of the reference's third entry point (PyMIC/pymic/net_run_wsl/; loss/seg/gatedcrf.py, loss/seg/ssl.py:46-86
+ * TotalVariationLoss, loss/seg/mumford_shah.py).  Logits fp32 [N][C][D][H][W] contiguous, 2 <= C <= 8; the image fp32
+ * [N][Ci][D][H][W], 1 <= Ci <= 4; a slice is one (n, d) plane and the kernels index the 5-D tensors directly (the reference
+ * transposes and copies to [N D][C][H][W]).  softmax = 1: softmax over C inside the kernel; 0: the input holds probabilities.
+ * Reductions: fp32 block partials in `part`, summed in double in a fixed order by one wave - no floating-point atomics, two
+ * runs give the same bits (the integer atomics on TV's count tensor commute).  out: double [4] on the device.  gscale: device
+ * fp32 scalar.  dlogits_c = gscale[0] p_c (e_c - sum_j p_j e_j) with e = dLoss/dp (softmax = 0: gscale[0] e_c).
+ * Limits: D H W <= 2^30, N C <= 65535, N D <= 65535.  FPLX_E_BADSHAPE / FPLX_E_NULL before any launch.
+ *  wsl_gatedcrf_fwd: GatedCRFLoss.forward with the Potts shortcut and no masks.  desc: host fp32 [nk][3] = (weight, sigma_xy,
+ *             sigma_rgb), 1 <= nk <= 4; a sigma of 0: that modality is absent (at least one per descriptor); 1 <= radius <= 8.
+ *             For a pixel i of a slice and every window position j != i, |dy|, |dx| <= radius:
+ *               k_ij = sum_desc weight exp(-1/2 (|xy_i - xy_j|^2 / sigma_xy^2 + sum_ch (I_i - I_j)^2 / sigma_rgb^2)).
+ *             A j outside the slice still counts: the reference zero-pads its unfold, so such a j has xy = (0, 0), I = 0, p = 0.
+ *             out0 = sum_i sum_j k_ij (1 - [j inside] sum_c p_c(i) p_c(j)) (one sum of non-negative terms), out3 = N D H W,
+ *             out2 = loss = out0 / out3, out1 = 0.  kp fp32 [N][C][D][H][W]: kp_c(i) = sum_{j inside} k_ij p_c(j).
+ *             part: fp32 [N D ceil(H / 16) ceil(W / 16)] (one per 16 x 16 tile of a slice; fewer than 2^31).
+ *  wsl_gatedcrf_bwd: k is symmetric between pixels of the slice: e_c(i) = -2 kp_c(i) / out3.  The image takes no gradient.
+ *  wsl_tv_fwd: TotalVariationLoss.forward for 5-D input: p' = 0.999 p + 5e-4 (a product, then a sum), e_v = min of p' over the
+ *             in-bounds 3x3x3 window, o_v = max of e over the in-bounds window, contour_v = relu(o_v - e_v); out0 = sum contour,
+ *             out3 = N C D H W, out2 = out0 / out3.  count int32 [N][C][D][H][W]: every voxel with contour_v > 0 adds +1 at the
+ *             p' voxel whose value o_v is and -1 at the argmin of its own window; equal values take the first in (d, h, w) scan
+ *             order, as torch's pooling does.  ws: at least 12 N C D H W bytes (p', e, the argmin offsets), 16-byte aligned.
+ *             part: fp32 [N C][fplx_loss_rows(D H W)].
+ *  wsl_tv_bwd: e_c = 0.999 count_c / (N C D H W).
+ *  wsl_mumford_shah_fwd: MumfordShahLoss.forward.  Per slice, class c, image channel ch: S0 = sum p_c, S1 = sum I_ch p_c over
+ *             H x W, cen = S1 / S0 (no epsilon, as in the reference), level = sum (I_ch - cen)^2 p_c in a second pass.
+ *             out0 = sum level; out1 = sum |p(h+1, w) - p(h, w)| + sum |p(h, w+1) - p(h, w)| inside the slice (penalty = 1) or
+ *             their squares (penalty = 2); out3 = N C D H W; out2 = (out0 + lambda out1) / out3.  cen fp32 [N][D][Ci][C].
+ *             part: fp32 [N D][fplx_loss_rows(H W)][C (1 + Ci)] (the moments; the loss pass reuses the front of it).
+ *  wsl_mumford_shah_bwd: e_c(v) = (sum_ch (I_ch(v) - cen)^2 + lambda stencil_v) / out3 (the centroid's own derivative is 0:
+ *             sum (I - cen) p = 0); stencil = sign(p_v - p_up) - sign(p_down - p_v) + the same along W, sign(0) = 0 (penalty 1),
+ *             2 (p_v - p_up) - 2 (p_down - p_v) + the same along W (penalty 2); differences that leave the slice are absent. */
+int fplx_wsl_gatedcrf_fwd(const float* logits, const float* image, int n, int c, int ci, int d, int h, int w, const float* desc,
+                          int nk, int radius, int softmax, float* kp, float* part, double* out, fplx_stream_t stream);
+int fplx_wsl_gatedcrf_bwd(const float* logits, const float* kp, const float* gscale, int n, int c, int d, int h, int w,
+                          int softmax, float* dlogits, fplx_stream_t stream);
+int fplx_wsl_tv_fwd(const float* logits, int n, int c, int d, int h, int w, int softmax, int32_t* count, void* ws,
+                    size_t ws_bytes, float* part, double* out, fplx_stream_t stream);
+int fplx_wsl_tv_bwd(const float* logits, const int32_t* count, const float* gscale, int n, int c, int d, int h, int w,
+                    int softmax, float* dlogits, fplx_stream_t stream);
+int fplx_wsl_mumford_shah_fwd(const float* logits, const float* image, int n, int c, int ci, int d, int h, int w, int penalty,
+                              float lambda, int softmax, float* cen, float* part, double* out, fplx_stream_t stream);
+int fplx_wsl_mumford_shah_bwd(const float* logits, const float* image, const float* cen, const float* gscale, int n, int c,
+                              int ci, int d, int h, int w, int penalty, float lambda, int softmax, float* dlogits,
+                              fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
