@@ -20,24 +20,7 @@ inline int it_grid(int64_t total) {
   return (int)(g > IT_MAX_BLOCKS ? IT_MAX_BLOCKS : (g < 1 ? 1 : g));
 }
 
-// ---- order-preserving integer keys of fp32 values.  Negative floats: all bits flipped; others: sign bit set.  -0.0 and
-// +0.0 get adjacent keys (0x7FFFFFFF, 0x80000000): they compare equal as values, which is all numpy's sort promises.
-// Every NaN maps to ONE key at the end its consumer needs: 0xFFFFFFFF (above +inf: numpy sorts NaN last, max propagates it)
-// or 0 (below -inf: min propagates it).  Neither is the key of a number, and both decode to a NaN.
-__device__ __forceinline__ uint32_t key_nan_high(float f) {
-  if (f != f) return 0xFFFFFFFFu;
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t key_nan_low(float f) {
-  if (f != f) return 0u;
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
+// (the order-preserving integer keys key_nan_high / key_nan_low / key_to_float: common.h)
 __device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64); v = t < v ? t : v; }

@@ -3,7 +3,8 @@
 // voxel, the kernel that reduces the partial rows (seg_loss_sums_k: an anonymous-namespace kernel, so each of the two files compiles
 // its own copy of it into the library), the first family's part of the one-thread finalize and the first family's gradient
 // terms of the backward voxel loop.  The rest of the voxel loops stays in their own files (loss_ext.hip says why).
-// ssl.hip (the semi-supervised passes) takes the limits, loss_rows / grid1 and softmax_argmax from here and nothing else.
+// ssl.hip and nll.hip (the semi-supervised and noisy-label passes) take the limits, loss_rows / grid1, softmax_argmax and the
+// voxel loads / stores from here and nothing else.
 #pragma once
 #include "common.h"
 
@@ -66,6 +67,44 @@ __device__ __forceinline__ int softmax_argmax(const float (&l)[MAXC], float (&p)
   for (int c = 1; c < C; ++c)
     if (p[c] > best) { best = p[c]; a = c; }
   return a;
+}
+
+// ---- what ssl.hip and nll.hip load and store voxels with: one voxel per lane, or four with 16-byte accesses
+template <int W> struct VecLd;
+template <> struct VecLd<1> {
+  static __device__ __forceinline__ void ld(const float* p, float (&o)[1]) { o[0] = *p; }
+  static __device__ __forceinline__ void st(float* p, const float (&o)[1]) { *p = o[0]; }
+};
+template <> struct VecLd<4> {
+  static __device__ __forceinline__ void ld(const float* p, float (&o)[4]) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+  }
+  static __device__ __forceinline__ void st(float* p, const float (&o)[4]) {
+    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+};
+
+// [C][V] rows of one sample at voxel v -> l[j][c] for the W voxels of this lane
+template <int C, int W>
+__device__ __forceinline__ void load_voxels(const float* __restrict__ base, int64_t V, int64_t v, float (&l)[W][MAXC]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float t[W];
+    VecLd<W>::ld(base + (int64_t)c * V + v, t);
+#pragma unroll
+    for (int j = 0; j < W; ++j) l[j][c] = t[j];
+  }
+}
+template <int C, int W>
+__device__ __forceinline__ void store_voxels(float* __restrict__ base, int64_t V, int64_t v, const float (&l)[W][MAXC]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float t[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) t[j] = l[j][c];
+    VecLd<W>::st(base + (int64_t)c * V + v, t);
+  }
 }
 
 // The first family's gradient terms of one class at one voxel, before the softmax Jacobian (ent_sm: the entropy term shares

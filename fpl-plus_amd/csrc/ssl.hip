@@ -4,50 +4,14 @@
 // Layouts and formulas: include/fplx.h, "semi-supervised learning".  Reductions as in the two loss families: a block's fp32
 // partial row, the rows summed in double in a fixed order by one wave (no floating-point atomics: two runs give the same bits).
 // A lane takes 4 consecutive voxels with 16-byte loads where every row of the tensors is 16-byte aligned (aligned bases and
-// V a multiple of 4), else one voxel; the flat passes (perturb, EMA) take n / 4 quads and a scalar tail.
+// V a multiple of 4), else one voxel; the flat passes (perturb, EMA) take n / 4 quads and a scalar tail
+// (VecLd, load_voxels, store_voxels: loss_common.h).
 // Compiled with -ffp-contract=off (Makefile): x + clamp(sigma z) must round as torch's three fp32 operations do, and the
 // sums of squares must not depend on what the compiler fuses; the fused multiply-adds that are meant are written as fmaf.
 #include "loss_common.h"
 #include "philox.h"
 
 namespace {
-
-template <int W> struct VecLd;
-template <> struct VecLd<1> {
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[1]) { o[0] = *p; }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[1]) { *p = o[0]; }
-};
-template <> struct VecLd<4> {
-  static __device__ __forceinline__ void ld(const float* p, float (&o)[4]) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float (&o)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-  }
-};
-
-// [C][V] rows of one sample at voxel v -> l[j][c] for the W voxels of this lane
-template <int C, int W>
-__device__ __forceinline__ void load_voxels(const float* __restrict__ base, int64_t V, int64_t v, float (&l)[W][MAXC]) {
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float t[W];
-    VecLd<W>::ld(base + (int64_t)c * V + v, t);
-#pragma unroll
-    for (int j = 0; j < W; ++j) l[j][c] = t[j];
-  }
-}
-template <int C, int W>
-__device__ __forceinline__ void store_voxels(float* __restrict__ base, int64_t V, int64_t v, const float (&l)[W][MAXC]) {
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float t[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) t[j] = l[j][c];
-    VecLd<W>::st(base + (int64_t)c * V + v, t);
-  }
-}
 
 // a block's K sums -> part[(n * gridDim.x + blockIdx.x) * K + k]
 template <int K>

@@ -26,7 +26,9 @@ from .ssl import (SSLSegAgent, SSLEntropyMinimization, SSLMeanTeacher, SSLUncert
                   SSLMethodDict, EntropyLoss, consistency_loss, ema_update, get_rampup_ratio)
 from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMumfordShah, WSLGatedCRF, WSLUSTM,  # noqa: E402
                   WSLMethodDict, TotalVariationLoss, MumfordShahLoss, GatedCRFLoss)
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl              # noqa: E402
+from .nll import (NLLSegAgent, NLLCoTeaching, NLLTriNet, NLLMethodDict, nll_agent_class, BiNet, TriNet,          # noqa: E402
+                  GroupOptimizer, selective_ce_loss)
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll         # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -38,4 +40,6 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "ssl", "SSLSegAgent", "SSLEntropyMinimization", "SSLMeanTeacher", "SSLUncertaintyAwareMeanTeacher", "SSLMethodDict",
            "EntropyLoss", "consistency_loss", "ema_update", "get_rampup_ratio",
            "wsl", "WSLSegAgent", "WSLEntropyMinimization", "WSLTotalVariation", "WSLMumfordShah", "WSLGatedCRF", "WSLUSTM",
-           "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss"]
+           "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss",
+           "nll", "NLLSegAgent", "NLLCoTeaching", "NLLTriNet", "NLLMethodDict", "nll_agent_class", "BiNet", "TriNet",
+           "GroupOptimizer", "selective_ce_loss"]

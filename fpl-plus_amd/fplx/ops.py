@@ -1011,8 +1011,9 @@ def set_weight_(pixel_weight, image_weight):
     return pixel_weight
 
 
-def overlap_counts(seg, gt, labels, fuse=False):
-    """exact voxel counts [rows, 3] = (|seg==l & gt==l|, |seg==l|, |gt==l|) as python ints (one device->host copy)"""
+def overlap_counts(seg, gt, labels, fuse=False, on_device=False):
+    """exact voxel counts [rows, 3] = (|seg==l & gt==l|, |seg==l|, |gt==l|) as python ints (one device->host copy), or with
+    on_device the int64 device tensor (no copy: a training loop that reads the host once per round)"""
     require_gpu(seg, gt)
     if seg.shape != gt.shape:
         raise ValueError("fplx: segmentation and ground truth shapes differ")
@@ -1022,7 +1023,7 @@ def overlap_counts(seg, gt, labels, fuse=False):
     rows = 1 if fuse else lab.numel()
     out = torch.empty((rows, 3), dtype=torch.int64, device=s.device)
     call("fplx_overlap_counts", ptr(s), ptr(g), s.numel(), ptr(lab), lab.numel(), 1 if fuse else 0, ptr(out), stream())
-    return out.tolist()
+    return out if on_device else out.tolist()
 
 
 def edge_points(mask):
@@ -1280,4 +1281,113 @@ def wsl_mumford_shah_bwd(logits, image, cen, gscale, penalty=1, lam=1.0, softmax
     dlogits = torch.empty_like(logits) if dlogits is None else dlogits
     call("fplx_wsl_mumford_shah_bwd", ptr(logits), ptr(image), ptr(cen), ptr(gscale), n, c, ci, d, h, w, int(penalty), float(lam),
          1 if softmax else 0, ptr(dlogits), stream())
+    return dlogits
+
+
+# ---- noisy-label learning (include/fplx.h, "noisy-label learning"; csrc/nll.hip)
+NLL_RANK, NLL_BELOW = 0, 1                          # FPLX_NLL_RANK / FPLX_NLL_BELOW
+NLL_USES = {"CoTeaching": (2, 1), "TriNet": (6, 5, 3)}       # bit i of uses[j]: mask i gates network j
+
+
+def _ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _nll_list(ts, what):
+    ts = list(ts)
+    if not 1 <= len(ts) <= 3:
+        raise ValueError("fplx nll: {0:} takes 1 to 3 tensors, got {1:}".format(what, len(ts)))
+    for t in ts[1:]:
+        if t.shape != ts[0].shape:
+            raise ValueError("fplx nll: {0:} differ in shape: {1:} and {2:}".format(what, tuple(ts[0].shape), tuple(t.shape)))
+    return ts
+
+
+def nll_quantile_rank(q, n):
+    """where torch.quantile(x, q) looks in the sorted float32 array of n values -> (k, w): the result is torch's lerp of s[k] and
+    s[k + 1] with the weight w.  torch makes q a tensor of the input's dtype, so pos = float32(q) * float32(n - 1) is rounded
+    to float32 (beyond n = 2^24 the rank itself is rounded: torch's choice, kept); k = floor(pos), w = pos - k.  A pos that
+    float32(n - 1) rounded past the last element reads the last element."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("quantile() q values must be in the range [0, 1]")
+    pos = np.float32(q) * np.float32(n - 1)
+    k = np.floor(pos)
+    if k >= n - 1:
+        return n - 1, 0.0
+    return int(k), float(np.float32(pos - k))
+
+
+def nll_voxel_ce_fwd(logits_list, label, loss=None, part=None):
+    """K logit tensors [N, C, ...] and one soft label of that shape -> (loss: list of K fp32 [N V], the per-voxel cross entropy
+    -sum_c y_c ln(0.999 p_c + 5e-4) in reshape_tensor_to_2D's voxel order; part fp32 [K, N, fplx_nll_ce_rows(V)], the partials of
+    their sums)"""
+    ls = _nll_list(logits_list, "logits")
+    _ssl_f32(label, *ls)
+    n, c, v = _ncv(ls[0])
+    if label.shape != ls[0].shape:
+        raise ValueError("fplx nll: label {0:} and logits {1:} differ in shape".format(tuple(label.shape), tuple(ls[0].shape)))
+    dev = label.device
+    loss = [torch.empty(n * v, dtype=torch.float32, device=dev) for _ in ls] if loss is None else loss
+    part = torch.empty((len(ls), n, _lib.lib().fplx_nll_ce_rows(v)), dtype=torch.float32, device=dev) if part is None else part
+    call("fplx_nll_voxel_ce_fwd", _ptrs(ls), len(ls), ptr(label), n, c, v, _ptrs(loss), ptr(part), stream())
+    return loss, part
+
+
+def nll_select_mask(loss, mode, num_remb=0, q=None, mask=None):
+    """loss fp32 [n] -> mask uint8 [n].  NLL_RANK: the first num_remb entries of a stable ascending argsort (CoTeaching's
+    ind_sorted[:num_remb]); NLL_BELOW: loss < torch.quantile(loss, q) (TriNet).  The order statistics come from select_kth
+    and stay on the device."""
+    _chan(loss)
+    n = loss.numel()
+    mask = torch.empty(n, dtype=torch.uint8, device=loss.device) if mask is None else mask
+    if mode == NLL_RANK:
+        num_remb = int(num_remb)
+        if not 0 <= num_remb <= n:
+            raise ValueError("fplx nll_select_mask: num_remb = {0:} outside [0, {1:}]".format(num_remb, n))
+        sk = ws = None
+        nb = _lib.lib().fplx_nll_mask_ws_bytes()
+        if num_remb > 0:
+            sk = select_kth(loss, [num_remb - 1])
+            ws = torch.empty(nb // 4, dtype=torch.int32, device=loss.device)
+        call("fplx_nll_select_mask", ptr(loss), n, NLL_RANK, num_remb, 0.0, ptr(sk), 0, ptr(mask), ptr(ws), nb, stream())
+    elif mode == NLL_BELOW:
+        k, w = nll_quantile_rank(q, n)
+        sk = select_kth(loss, [k, n - 1])                   # the largest rides along: NaN sorts last
+        call("fplx_nll_select_mask", ptr(loss), n, NLL_BELOW, 0, w, ptr(sk), sk[1].data_ptr(), ptr(mask), 0, 0, stream())
+    else:
+        raise ValueError("fplx nll_select_mask: mode {0:} (NLL_RANK, NLL_BELOW)".format(mode))
+    return mask
+
+
+def nll_select_fwd(loss, masks, uses, part, out=None):
+    """K losses [n], K masks [n], uses[j] = bit set of the masks that gate network j, part = nll_voxel_ce_fwd's -> out double
+    [K, 4]: sum of the kept loss_j, number kept, their mean (NaN for an empty selection), sum of all loss_j"""
+    loss, masks = _nll_list(loss, "losses"), list(masks)
+    require_gpu(part, *(loss + masks))
+    k, n = len(loss), loss[0].numel()
+    if len(masks) != k or len(uses) != k or any(m.numel() != n or m.dtype != torch.uint8 for m in masks):
+        raise ValueError("fplx nll_select_fwd: {0:} losses need {0:} uint8 masks of {1:} elements and {0:} uses".format(k, n))
+    if part.numel() % k:
+        raise ValueError("fplx nll_select_fwd: part has {0:} elements for {1:} networks".format(part.numel(), k))
+    dev = loss[0].device
+    out = torch.empty((k, 4), dtype=torch.float64, device=dev) if out is None else out
+    nb = _lib.lib().fplx_nll_select_ws_bytes()
+    ws = torch.empty(nb // 4, dtype=torch.int32, device=dev)
+    call("fplx_nll_select_fwd", _ptrs(loss), _ptrs(masks), (ctypes.c_int * k)(*[int(u) for u in uses]), k, n, ptr(part),
+         part.numel() // k, ptr(out), ptr(ws), nb, stream())
+    return out
+
+
+def nll_select_bwd(logits_list, label, masks, uses, out, gscale, wj, dlogits=None):
+    """-> K tensors dlogits_j = gscale[0] wj d(mean of the kept loss_j) / dlogits_j of the forward that wrote `out`"""
+    ls, masks = _nll_list(logits_list, "logits"), list(masks)
+    _ssl_f32(label, gscale, *ls)
+    require_gpu(out, *masks)
+    n, c, v = _ncv(ls[0])
+    k = len(ls)
+    if len(masks) != k or len(uses) != k or any(m.numel() != n * v or m.dtype != torch.uint8 for m in masks):
+        raise ValueError("fplx nll_select_bwd: {0:} logits need {0:} uint8 masks of {1:} elements and {0:} uses".format(k, n * v))
+    dlogits = [torch.empty_like(t) for t in ls] if dlogits is None else dlogits
+    call("fplx_nll_select_bwd", _ptrs(ls), ptr(label), _ptrs(masks), (ctypes.c_int * k)(*[int(u) for u in uses]), k, ptr(out),
+         ptr(gscale), float(wj), n, c, v, _ptrs(dlogits), stream())
     return dlogits

@@ -806,6 +806,52 @@ int fplx_wsl_mumford_shah_bwd(const float* logits, const float* image, const flo
                               int ci, int d, int h, int w, int penalty, float lambda, int softmax, float* dlogits,
                               fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ noisy-label learning (csrc/nll.hip)
+ * The selection losses of the reference's fourth entry point (PyMIC/pymic/net_run_nll/nll_co_teaching.py:91-118 CoTeaching,
+ * nll_trinet.py:66-120 TriNet) over K = 1..3 networks.  Logits and the soft label fp32 [N][C][V] contiguous, 2 <= C <= 8,
+ * 1 <= N <= 65535, N V < 2^31 (the bound of fplx_select_kth); a voxel has the flat index n V + v, the row order of the
+ * reference's reshape_tensor_to_2D.  `logits`, `loss`, `mask`, `dlogits`: HOST arrays of K device pointers.  A lane takes four
+ * voxels with 16-byte accesses where every base is 16-byte aligned and V is a multiple of 4, else one voxel.  Reductions: fp32
+ * block partials summed in double in a fixed order by one wave, counts in integers - no floating-point atomics, two runs
+ * give the same bits.  FPLX_E_NULL / FPLX_E_BADSHAPE / FPLX_E_WORKSPACE before any launch.
+ *  nll_voxel_ce_fwd: ONE launch for all K, the label read once.  p = softmax(logits_k), p'_c = 0.999 p_c + 5e-4 (a product, then a
+ *             sum, as torch's), loss_k[n V + v] = sum_c (-y_c) ln p'_c (c ascending).  part fp32 [K][N][fplx_nll_ce_rows(V)]: the
+ *             block sums of loss_k, the partials of the reference's loss_no_select (nll_select_fwd adds them up).
+ *  nll_select_mask: loss fp32 [n] -> mask uint8 [n] (1 = kept) from the order statistics fplx_select_kth wrote on the device.
+ *             FPLX_NLL_RANK (CoTeaching, `ind_sorted[:num_remb]`): sk[0] = s[num_remb - 1] = t.  Kept: every voxel with
+ *             loss < t and, of the voxels with loss == t, the first num_remb - #{loss < t} in index order - exactly num_remb
+ *             voxels, the first num_remb entries of a STABLE ascending argsort.  Comparisons on select_kth's order-preserving
+ *             integer key (all NaNs equal and last).  num_remb = n keeps all; num_remb = 0 keeps none (sk, ws may be NULL).
+ *             Three passes - count, scan, write - in which every block owns the same contiguous chunk of the array; ws: at
+ *             least fplx_nll_mask_ws_bytes().  w, smax are ignored.
+ *             FPLX_NLL_BELOW (TriNet, `loss < torch.quantile(loss, q)`): sk = {s[k], s[k + 1]}, w in [0, 1) from the host:
+ *             pos = float32(q) float32(n - 1) IN FP32 (torch makes q a tensor of the input's dtype), k = floor(pos),
+ *             w = pos - k.  thr = torch's lerp in fp32: a + w (b - a) for w < 0.5, else b - (b - a)(1 - w), with b = a for
+ *             w = 0 (torch gathers s[ceil(pos)]).  Kept iff loss < thr as fp32 values.  smax (optional): device s[n - 1]; if it
+ *             is NaN the array holds a NaN, torch.quantile returns NaN and nothing is kept.  num_remb, ws are ignored.
+ *  nll_select_fwd: ONE launch (after a memset node that clears its ticket).  loss_j fp32 [n], mask_j uint8 [n], uses[j]: bit i
+ *             set = mask_i gates network j, the kept set of j is the AND of its masks (CoTeaching {2, 1}; TriNet {6, 5, 3}).
+ *             out double [K][4]: sum of the kept loss_j; number kept; their quotient (0 / 0 = NaN, the mean of an empty
+ *             selection as in the reference); sum of ALL loss_j from ce_part [K][ce_rows] (nll_voxel_ce_fwd's part,
+ *             ce_rows = N fplx_nll_ce_rows(V)).  ws: at least fplx_nll_select_ws_bytes(); the block that draws the last ticket
+ *             adds the rows up.
+ *  nll_select_bwd: ONE launch for all K.  Softmax recomputed from the logits, count_j = out[j][1] read on the device:
+ *             e_c = -0.999 y_c / p'_c keep_j / count_j, dlogits_j,c = gscale[0] wj p_c (e_c - sum_i p_i e_i); an empty
+ *             selection gives zeros.  wj: 1 for CoTeaching (the sum of the two means), 1/3 for TriNet.  gscale: device fp32. */
+enum { FPLX_NLL_RANK = 0, FPLX_NLL_BELOW = 1 };
+int fplx_nll_ce_rows(int64_t voxels_per_sample);
+int fplx_nll_voxel_ce_fwd(const float* const* logits, int k, const float* label, int n, int c, int64_t voxels_per_sample,
+                          float* const* loss, float* part, fplx_stream_t stream);
+size_t fplx_nll_mask_ws_bytes(void);
+int fplx_nll_select_mask(const float* loss, int64_t n, int mode, int64_t num_remb, float w, const float* sk, const float* smax,
+                         uint8_t* mask, void* ws, size_t ws_bytes, fplx_stream_t stream);
+size_t fplx_nll_select_ws_bytes(void);
+int fplx_nll_select_fwd(const float* const* loss, const uint8_t* const* mask, const int* uses, int k, int64_t n,
+                        const float* ce_part, int64_t ce_rows, double* out, void* ws, size_t ws_bytes, fplx_stream_t stream);
+int fplx_nll_select_bwd(const float* const* logits, const float* label, const uint8_t* const* mask, const int* uses, int k,
+                        const double* out, const float* gscale, float wj, int n, int c, int64_t voxels_per_sample,
+                        float* const* dlogits, fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
