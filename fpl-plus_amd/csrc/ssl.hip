@@ -1,6 +1,7 @@
 // Semi-supervised regularisers of the reference's second entry point (PyMIC/pymic/net_run_ssl/ssl_em.py, ssl_mt.py, ssl_uamt.py):
 // the clamped-noise perturbation of a teacher input, the (uncertainty-masked) consistency loss between student and teacher,
 // EntropyLoss (loss/seg/ssl.py:32-44) and the EMA of the parameters - each ONE pass over its tensors, forward and backward.
+// Also URPC's pyramid consistency over K output scales (ssl_urpc.py:76-91) and CPS's one-hot pseudo labels (ssl_cps.py:103-106).
 // Layouts and formulas: include/fplx.h, "semi-supervised learning".  Reductions as in the two loss families: a block's fp32
 // partial row, the rows summed in double in a fixed order by one wave (no floating-point atomics: two runs give the same bits).
 // A lane takes 4 consecutive voxels with 16-byte loads where every row of the tensors is 16-byte aligned (aligned bases and
@@ -214,6 +215,195 @@ ssl_ent_bwd_k(const float* __restrict__ logits, const float* __restrict__ gscale
   }
 }
 
+// ---- URPC's pyramid consistency (ssl_urpc.py:76-91) over K = 2..4 full-resolution logit tensors, and CPS's pseudo labels.
+// Per voxel K C probabilities are live at once, so the vector path is four voxels per lane only while K C <= 12 and two
+// (8-byte accesses) beyond; the register counts per instantiation are in DESIGN 1n.
+constexpr int PYR_K = 4;
+struct PyrIn { const float* p[PYR_K]; };
+struct PyrOut { float* p[PYR_K]; };
+
+template <> struct VecLd<2> {
+  static __device__ __forceinline__ void ld(const float* p, float (&o)[2]) {
+    const float2 t = *reinterpret_cast<const float2*>(p);
+    o[0] = t.x; o[1] = t.y;
+  }
+  static __device__ __forceinline__ void st(float* p, const float (&o)[2]) { *reinterpret_cast<float2*>(p) = make_float2(o[0], o[1]); }
+};
+
+constexpr int pyr_width(int K, int C) { return K * C <= 12 ? 4 : 2; }
+// the backward pass also holds the K C gradients of every voxel until their rows are stored
+constexpr int pyr_width_bwd(int K, int C) { return K * C <= 4 ? 4 : (K * C <= 12 ? 2 : 1); }
+
+// one voxel in the reference's order: p_k = softmax(z_k), m = (p_1 + .. + p_K) / K, a = 0.99 m + 0.005, q_k = 0.99 p_k + 0.005,
+// dl_kc = ln a_c - ln q_kc, var_k = sum_c a_c dl_kc, e_k = exp(-var_k), s_k = sum_c (a_c - q_kc)^2
+template <int K, int C>
+__device__ __forceinline__ void pyr_voxel(const float (&l)[K][MAXC], float (&p)[K][MAXC], float (&a)[MAXC], float (&dl)[K][MAXC],
+                                          float (&var)[K], float (&e)[K], float (&s)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) softmax_argmax<C>(l[k], p[k], true);
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float m = p[0][c];
+#pragma unroll
+    for (int k = 1; k < K; ++k) m += p[k][c];
+    a[c] = (m / (float)K) * 0.99f + 0.005f;
+    const float la = logf(a[c]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) dl[k][c] = la - logf(p[k][c] * 0.99f + 0.005f);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float vs = 0.f, ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float d = a[c] - (p[k][c] * 0.99f + 0.005f);
+      vs += a[c] * dl[k][c];
+      ss += d * d;
+    }
+    var[k] = vs;
+    e[k] = expf(-vs);
+    s[k] = ss;
+  }
+}
+
+// part [N][rows][3 K]: per scale sum s_k e_k, sum e_k, sum var_k
+template <int K, int C, int W>
+__global__ void __launch_bounds__(LT)
+ssl_pyramid_fwd_k(PyrIn lg, int64_t V, float* __restrict__ part) {
+  const int64_t off = (int64_t)blockIdx.y * C * V;
+  float acc[3 * K];
+#pragma unroll
+  for (int i = 0; i < 3 * K; ++i) acc[i] = 0.f;
+  const int64_t nq = V / W;
+  for (int64_t i = (int64_t)blockIdx.x * LT + threadIdx.x; i < nq; i += (int64_t)gridDim.x * LT) {
+    float l[K][W][MAXC];
+#pragma unroll
+    for (int k = 0; k < K; ++k) load_voxels<C, W>(lg.p[k] + off, V, i * W, l[k]);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      float lv[K][MAXC], p[K][MAXC], a[MAXC], dl[K][MAXC], var[K], e[K], s[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < C; ++c) lv[k][c] = l[k][j][c];
+      pyr_voxel<K, C>(lv, p, a, dl, var, e, s);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        acc[3 * k + 0] += s[k] * e[k];
+        acc[3 * k + 1] += e[k];
+        acc[3 * k + 2] += var[k];
+      }
+    }
+  }
+  block_rows<3 * K>(acc, part);
+}
+
+// one wave: the rows in double, lanes stride over them; out [K][4] (A_k, B_k, V_k, L_k) + [2] (loss_reg, 0), M = N V:
+// L_k = (A_k / (C M)) / (B_k / M + 1e-8) + V_k / M (ssl_urpc.py:88-89), loss_reg = sum_k L_k / K
+__global__ void ssl_pyramid_finish_k(const float* __restrict__ part, int K, int C, int64_t rows_total, double M,
+                                     double* __restrict__ out) {
+  const int lane = threadIdx.x;
+  double total = 0.0;
+  for (int k = 0; k < K; ++k) {
+    double t[3];
+    for (int i = 0; i < 3; ++i) {
+      double s = 0.0;
+      for (int64_t r = lane; r < rows_total; r += 64) s += (double)part[r * (3 * K) + 3 * k + i];
+      t[i] = wave_sum_d(s);
+    }
+    const double L = (t[0] / (C * M)) / (t[1] / M + 1e-8) + t[2] / M;
+    total += L;
+    if (lane == 0) { out[4 * k + 0] = t[0]; out[4 * k + 1] = t[1]; out[4 * k + 2] = t[2]; out[4 * k + 3] = L; }
+  }
+  if (lane == 0) { out[4 * K] = total / K; out[4 * K + 1] = 0.0; }
+}
+
+// g_k = 1 / M - e_k (alpha_k s_k + beta_k) = dL_k / dvar_k, h_k = alpha_k e_k = dL_k / ds_k with alpha_k, beta_k from A_k, B_k
+// of `out`; the mean over the scales carries gradient (the reference does not detach it); then the softmax Jacobian
+template <int K, int C, int W>
+__global__ void __launch_bounds__(LT)
+ssl_pyramid_bwd_k(PyrIn lg, const double* __restrict__ out, const float* __restrict__ gscale, int N, int64_t V, PyrOut dlg) {
+  const int64_t off = (int64_t)blockIdx.y * C * V;
+  const double M = (double)N * (double)V, CM = (double)C * M;
+  float al[K], be[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const double den = out[4 * k + 1] / M + 1e-8;
+    al[k] = (float)(1.0 / (CM * den));
+    be[k] = (float)(-(out[4 * k] / CM) / (den * den) / M);
+  }
+  const float invM = (float)(1.0 / M), gs = *gscale, w = 0.99f / (float)K;
+  const int64_t nq = V / W;
+  for (int64_t i = (int64_t)blockIdx.x * LT + threadIdx.x; i < nq; i += (int64_t)gridDim.x * LT) {
+    float l[K][W][MAXC], d[K][W][MAXC];
+#pragma unroll
+    for (int k = 0; k < K; ++k) load_voxels<C, W>(lg.p[k] + off, V, i * W, l[k]);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      float lv[K][MAXC], p[K][MAXC], a[MAXC], dl[K][MAXC], var[K], e[K], s[K], g[K], h2[K], t[MAXC];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < C; ++c) lv[k][c] = l[k][j][c];
+      pyr_voxel<K, C>(lv, p, a, dl, var, e, s);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        g[k] = invM - e[k] * (al[k] * s[k] + be[k]);
+        h2[k] = 2.f * (al[k] * e[k]);
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        float ts = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) ts += g[k] * (dl[k][c] + 1.f) + h2[k] * (a[c] - (p[k][c] * 0.99f + 0.005f));
+        t[c] = ts / (float)K;
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        float gp[MAXC], dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const float q = p[k][c] * 0.99f + 0.005f;
+          gp[c] = w * (t[c] - g[k] * a[c] / q - h2[k] * (a[c] - q));
+          dot = fmaf(gp[c], p[k][c], dot);
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) d[k][j][c] = gs * (p[k][c] * (gp[c] - dot));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) store_voxels<C, W>(dlg.p[k] + off, V, i * W, d[k]);
+  }
+}
+
+// fp32 one-hot of the first maximum of the LOGITS over C, K tensors in one launch (ssl_cps.py:103-106)
+template <int C, int W>
+__global__ void __launch_bounds__(LT)
+ssl_pseudo_onehot_k(PyrIn lg, int K, int64_t V, PyrOut oh) {
+  const int64_t off = (int64_t)blockIdx.y * C * V;
+  const int64_t nq = V / W;
+  for (int64_t i = (int64_t)blockIdx.x * LT + threadIdx.x; i < nq; i += (int64_t)gridDim.x * LT) {
+#pragma unroll
+    for (int k = 0; k < PYR_K - 1; ++k) {
+      if (k < K) {
+        float l[W][MAXC], o[W][MAXC];
+        load_voxels<C, W>(lg.p[k] + off, V, i * W, l);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          int best = 0;
+          float m = l[j][0];
+#pragma unroll
+          for (int c = 1; c < C; ++c)
+            if (l[j][c] > m) { m = l[j][c]; best = c; }
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[j][c] = c == best ? 1.f : 0.f;
+        }
+        store_voxels<C, W>(oh.p[k] + off, V, i * W, o);
+      }
+    }
+  }
+}
+
 // ---- flat passes
 __device__ __forceinline__ float perturb1(float x, float z, float sigma, float clip) {
   const float t = sigma * z;
@@ -288,6 +478,48 @@ inline int ssl_shape_check(const char* what, int n, int c, int64_t v) {
 
 inline int ssl_t_check(const char* what, int t) {
   FPLX_REQUIRE(t >= 0 && t <= 16 && (t & 1) == 0, FPLX_E_BADSHAPE, "%s: t=%d Monte-Carlo passes (even, 0..16)", what, t);
+  return FPLX_OK;
+}
+
+// K and C to template arguments; the vector path's width is pyr_width(K, C)
+template <int K, int C>
+void pyr_launch_fwd(bool vec, dim3 grid, hipStream_t st, const PyrIn& in, int64_t v, float* part) {
+  if (vec) ssl_pyramid_fwd_k<K, C, pyr_width(K, C)><<<grid, LT, 0, st>>>(in, v, part);
+  else ssl_pyramid_fwd_k<K, C, 1><<<grid, LT, 0, st>>>(in, v, part);
+}
+template <int K, int C>
+void pyr_launch_bwd(bool vec, int n, hipStream_t st, const PyrIn& in, const double* out, const float* gscale, int64_t v,
+                    const PyrOut& o) {
+  constexpr int W = pyr_width_bwd(K, C);
+  if (vec) ssl_pyramid_bwd_k<K, C, W><<<dim3(grid1(v / W, 2048), n), LT, 0, st>>>(in, out, gscale, n, v, o);
+  else ssl_pyramid_bwd_k<K, C, 1><<<dim3(grid1(v, 2048), n), LT, 0, st>>>(in, out, gscale, n, v, o);
+}
+#define PYR_C(K, C, FN, ...)                     \
+  switch (C) {                                   \
+    case 2: FN<K, 2>(__VA_ARGS__); break;        \
+    case 3: FN<K, 3>(__VA_ARGS__); break;        \
+    case 4: FN<K, 4>(__VA_ARGS__); break;        \
+    case 5: FN<K, 5>(__VA_ARGS__); break;        \
+    case 6: FN<K, 6>(__VA_ARGS__); break;        \
+    case 7: FN<K, 7>(__VA_ARGS__); break;        \
+    default: FN<K, 8>(__VA_ARGS__); break;       \
+  }
+#define PYR_DISPATCH(K, C, FN, ...)              \
+  switch (K) {                                   \
+    case 2: PYR_C(2, C, FN, __VA_ARGS__) break;  \
+    case 3: PYR_C(3, C, FN, __VA_ARGS__) break;  \
+    default: PYR_C(4, C, FN, __VA_ARGS__) break; \
+  }
+
+// the table's first k entries -> a by-value struct; refuses a NULL entry; *vec stays true while every base is 16-byte aligned
+template <typename S, typename T>
+int pyr_table(const char* what, T* const* table, int k, S* s, bool* vec) {
+  for (int j = 0; j < PYR_K; ++j) s->p[j] = nullptr;
+  for (int j = 0; j < k; ++j) {
+    FPLX_REQUIRE(table[j], FPLX_E_NULL, "%s: null tensor %d", what, j);
+    s->p[j] = table[j];
+    *vec = *vec && aligned16(table[j]);
+  }
   return FPLX_OK;
 }
 
@@ -384,6 +616,57 @@ int fplx_ssl_entropy_bwd(const float* logits, const float* gscale, int n, int c,
   dim3 grid(grid1(vec ? v / 4 : v, 2048), n);
   SSL_DISPATCH_VEC(vec, c, ssl_ent_bwd_k, <<<grid, LT, 0, (hipStream_t)stream>>>(logits, gscale, coef, v, softmax, dlogits));
   return fplx_check_launch("ssl_entropy_bwd");
+}
+
+int fplx_ssl_pyramid_fwd(const float* const* logits, int k, int n, int c, int64_t v, float* part, double* out,
+                         fplx_stream_t stream) {
+  FPLX_REQUIRE(k >= 2 && k <= PYR_K, FPLX_E_BADSHAPE, "ssl_pyramid_fwd: k=%d scales (2..%d)", k, PYR_K);
+  int rc = ssl_shape_check("ssl_pyramid_fwd", n, c, v);
+  if (rc != FPLX_OK) return rc;
+  FPLX_REQUIRE(logits && part && out, FPLX_E_NULL, "ssl_pyramid_fwd: null pointer");
+  PyrIn in;
+  bool vec = v % 4 == 0;
+  rc = pyr_table("ssl_pyramid_fwd", logits, k, &in, &vec);
+  if (rc != FPLX_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = loss_rows(v);
+  PYR_DISPATCH(k, c, pyr_launch_fwd, vec, dim3(rows, n), st, in, v, part);
+  ssl_pyramid_finish_k<<<1, 64, 0, st>>>(part, k, c, (int64_t)n * rows, (double)n * (double)v, out);
+  return fplx_check_launch("ssl_pyramid_fwd");
+}
+
+int fplx_ssl_pyramid_bwd(const float* const* logits, const double* out, const float* gscale, int k, int n, int c, int64_t v,
+                         float* const* dlogits, fplx_stream_t stream) {
+  FPLX_REQUIRE(k >= 2 && k <= PYR_K, FPLX_E_BADSHAPE, "ssl_pyramid_bwd: k=%d scales (2..%d)", k, PYR_K);
+  int rc = ssl_shape_check("ssl_pyramid_bwd", n, c, v);
+  if (rc != FPLX_OK) return rc;
+  FPLX_REQUIRE(logits && out && gscale && dlogits, FPLX_E_NULL, "ssl_pyramid_bwd: null pointer");
+  PyrIn in;
+  PyrOut o;
+  bool vec = v % 4 == 0;
+  rc = pyr_table("ssl_pyramid_bwd", logits, k, &in, &vec);
+  if (rc != FPLX_OK) return rc;
+  rc = pyr_table("ssl_pyramid_bwd", dlogits, k, &o, &vec);
+  if (rc != FPLX_OK) return rc;
+  PYR_DISPATCH(k, c, pyr_launch_bwd, vec, n, (hipStream_t)stream, in, out, gscale, v, o);
+  return fplx_check_launch("ssl_pyramid_bwd");
+}
+
+int fplx_ssl_pseudo_onehot(const float* const* logits, int k, int n, int c, int64_t v, float* const* onehot, fplx_stream_t stream) {
+  FPLX_REQUIRE(k >= 1 && k < PYR_K, FPLX_E_BADSHAPE, "ssl_pseudo_onehot: k=%d tensors (1..%d)", k, PYR_K - 1);
+  int rc = ssl_shape_check("ssl_pseudo_onehot", n, c, v);
+  if (rc != FPLX_OK) return rc;
+  FPLX_REQUIRE(logits && onehot, FPLX_E_NULL, "ssl_pseudo_onehot: null pointer");
+  PyrIn in;
+  PyrOut o;
+  bool vec = v % 4 == 0;
+  rc = pyr_table("ssl_pseudo_onehot", logits, k, &in, &vec);
+  if (rc != FPLX_OK) return rc;
+  rc = pyr_table("ssl_pseudo_onehot", onehot, k, &o, &vec);
+  if (rc != FPLX_OK) return rc;
+  dim3 grid(grid1(vec ? v / 4 : v, 2048), n);
+  SSL_DISPATCH_VEC(vec, c, ssl_pseudo_onehot_k, <<<grid, LT, 0, (hipStream_t)stream>>>(in, k, v, o));
+  return fplx_check_launch("ssl_pseudo_onehot");
 }
 
 int fplx_ema_step(float* ema, const float* p, int64_t n, float alpha, fplx_stream_t stream) {

@@ -23,12 +23,13 @@ from .config import parse_config, synchronize_config               # noqa: E402
 from .dataset import NiftyDataset                                  # noqa: E402
 from .postprocess import PostProcess, PostKeepLargestComponent, PostProcessDict, get_largest_k_components  # noqa: E402
 from .ssl import (SSLSegAgent, SSLEntropyMinimization, SSLMeanTeacher, SSLUncertaintyAwareMeanTeacher,   # noqa: E402
-                  SSLMethodDict, EntropyLoss, consistency_loss, ema_update, get_rampup_ratio)
+                  SSLMethodDict, EntropyLoss, consistency_loss, ema_update, get_rampup_ratio,
+                  SSLCPS, SSLURPC, SSLMethodDictAll, ssl_agent_class_all, pyramid_consistency_loss, cross_pseudo_labels)
 from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMumfordShah, WSLGatedCRF, WSLUSTM,  # noqa: E402
                   WSLMethodDict, TotalVariationLoss, MumfordShahLoss, GatedCRFLoss)
 from .nll import (NLLSegAgent, NLLCoTeaching, NLLTriNet, NLLMethodDict, nll_agent_class, BiNet, TriNet,          # noqa: E402
                   GroupOptimizer, selective_ce_loss)
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll         # noqa: E402
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup         # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -39,6 +40,8 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "MSELoss", "SLSRLoss", "DeepSuperviseLoss", "UNet2D5", "UNet3D", "PostProcess", "PostKeepLargestComponent", "PostProcessDict", "get_largest_k_components",
            "ssl", "SSLSegAgent", "SSLEntropyMinimization", "SSLMeanTeacher", "SSLUncertaintyAwareMeanTeacher", "SSLMethodDict",
            "EntropyLoss", "consistency_loss", "ema_update", "get_rampup_ratio",
+           "SSLCPS", "SSLURPC", "SSLMethodDictAll", "ssl_agent_class_all", "pyramid_consistency_loss", "cross_pseudo_labels",
+           "netgroup",
            "wsl", "WSLSegAgent", "WSLEntropyMinimization", "WSLTotalVariation", "WSLMumfordShah", "WSLGatedCRF", "WSLUSTM",
            "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss",
            "nll", "NLLSegAgent", "NLLCoTeaching", "NLLTriNet", "NLLMethodDict", "nll_agent_class", "BiNet", "TriNet",

@@ -1186,6 +1186,54 @@ def ema_step(ema, p, alpha):
     return ema
 
 
+def _ssl_table(ts, what, lo, hi):
+    """K contiguous fp32 tensors of one shape -> (list, n, c, v)"""
+    ts = list(ts)
+    if not lo <= len(ts) <= hi:
+        raise ValueError("fplx ssl: {0:} takes {1:} to {2:} logit tensors, got {3:}".format(what, lo, hi, len(ts)))
+    _ssl_f32(*ts)
+    for t in ts[1:]:
+        if t.shape != ts[0].shape:
+            raise ValueError("fplx ssl: {0:}: the logit tensors differ in shape: {1:} and {2:}".format(
+                what, tuple(ts[0].shape), tuple(t.shape)))
+    return (ts,) + _ncv(ts[0])
+
+
+def ssl_pyramid_fwd(logits_list, part=None, out=None):
+    """URPC's regulariser (ssl_urpc.py:76-91) over K = 2..4 logit tensors [N, C, ...] (the unlabelled rows) -> out double
+    [4 K + 2]: per scale A_k, B_k, V_k, L_k; then loss_reg and 0 (include/fplx.h)"""
+    ls, n, c, v = _ssl_table(logits_list, "ssl_pyramid_fwd", 2, 4)
+    k = len(ls)
+    part = ssl_part(ls[0], 3 * k) if part is None else part
+    out = torch.empty(4 * k + 2, dtype=torch.float64, device=ls[0].device) if out is None else out
+    call("fplx_ssl_pyramid_fwd", _ptrs(ls), k, n, c, v, ptr(part), ptr(out), stream())
+    return out
+
+
+def ssl_pyramid_bwd(logits_list, out, gscale, dlogits=None):
+    """-> K tensors dlogits_j = gscale[0] d loss_reg / d logits_j of the forward that wrote `out`, in one launch"""
+    ls, n, c, v = _ssl_table(logits_list, "ssl_pyramid_bwd", 2, 4)
+    _ssl_f32(gscale)
+    require_gpu(out)
+    dlogits = [torch.empty_like(t) for t in ls] if dlogits is None else list(dlogits)
+    if len(dlogits) != len(ls):
+        raise ValueError("fplx ssl_pyramid_bwd: {0:} gradient tensors for {1:} logit tensors".format(len(dlogits), len(ls)))
+    _ssl_f32(*dlogits)
+    call("fplx_ssl_pyramid_bwd", _ptrs(ls), ptr(out), ptr(gscale), len(ls), n, c, v, _ptrs(dlogits), stream())
+    return dlogits
+
+
+def ssl_pseudo_onehot(logits_list, onehot=None):
+    """K = 1..3 logit tensors [N, C, ...] -> K fp32 one-hot tensors of the first maximum over C (ssl_cps.py:103-106), one launch"""
+    ls, n, c, v = _ssl_table(logits_list, "ssl_pseudo_onehot", 1, 3)
+    onehot = [torch.empty_like(t) for t in ls] if onehot is None else list(onehot)
+    if len(onehot) != len(ls):
+        raise ValueError("fplx ssl_pseudo_onehot: {0:} outputs for {1:} logit tensors".format(len(onehot), len(ls)))
+    _ssl_f32(*onehot)
+    call("fplx_ssl_pseudo_onehot", _ptrs(ls), len(ls), n, c, v, _ptrs(onehot), stream())
+    return onehot
+
+
 # ---- weakly-supervised learning (include/fplx.h, "weakly-supervised learning"; csrc/wsl.hip)
 _CRF_TILE = 16
 

@@ -15,9 +15,18 @@ optimiser and scheduler step before the EMA, alpha = min(1 - 1 / (iter_max + 1),
 that stays in train mode, takes no gradient and is not saved.
 Different, on purpose (DESIGN 1k): an odd uamt_mcdroput_n is refused (the reference averages an all-zero slot in);
 EntropyLoss() can be constructed (the reference's cannot under a current torch) and applies softmax as ssl_em.py:76 asks;
-DSBN networks and torch.distributed groups are refused; CCT / CPS / URPC are refused (they need networks the registry does
-not hold).  The teacher's dropout stream is seeded with the student's dropout_seed + 1.
+DSBN networks and torch.distributed groups are refused.  The teacher's dropout stream is seeded with the student's
+dropout_seed + 1.
+
+CPS and URPC (DESIGN 1n; ssl_cps.py:31-176, ssl_urpc.py:14-122) are registered in SSLMethodDictAll / ssl_agent_class_all;
+SSLMethodDict and ssl_agent_class keep the first three methods.  URPC runs on UNet3D / UNet2D5 with [network] deep_supervise =
+True (the reference's UNet2D_URPC is not in its tree): its regulariser over the K output scales is `pyramid_consistency_loss`,
+ONE autograd node on fplx_ssl_pyramid_fwd / _bwd.  CPS runs a BiNet under a GroupOptimizer (fplx/netgroup.py); its pseudo
+labels come from fplx_ssl_pseudo_onehot, the argmax of the LOGITS (two distinct logits that fp32 softmax rounds to one
+probability keep their order here; the reference takes the first of the pair).  CCT stays refused: its auxiliary-decoder
+network (pymic.net.net2d) is in neither tree.
 """
+import logging
 import math
 
 import numpy as np
@@ -28,7 +37,9 @@ from torch.optim import lr_scheduler
 from . import ops
 from .agent import SegmentationAgent
 from .dataset import NiftyDataset, BatchLoader
+from .netgroup import BiNet, GroupOptimizer, _DSBN_NAMES
 from .nets3d import UNet2D5, UNet3D
+from .optim import get_optimizer
 from .transform import Compose
 
 
@@ -137,8 +148,63 @@ def ema_update(net_ema, net, alpha):
     net_ema.parameters_changed()                   # the teacher's packs are rebuilt from the new values
 
 
+class _Pyramid(torch.autograd.Function):
+    """fplx_ssl_pyramid_fwd / _bwd as one autograd node over the K joint-batch tensors; rows < n0 receive zeros"""
+
+    @staticmethod
+    def forward(ctx, n0, holder, *outputs):
+        full = [t.float().contiguous() for t in outputs]
+        out = ops.ssl_pyramid_fwd([t[n0:] for t in full])           # N is outermost: the unlabelled rows are contiguous views
+        ctx.save_for_backward(out, *full)
+        ctx.n0 = n0
+        if holder is not None:
+            holder["out"] = out
+        return out[4 * len(full)].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        out, full = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        grads = [torch.empty_like(t) for t in full]
+        for d in grads:
+            d[:ctx.n0].zero_()
+        ops.ssl_pyramid_bwd([t[ctx.n0:] for t in full], out, g.float().contiguous().reshape(1), [d[ctx.n0:] for d in grads])
+        return (None, None) + tuple(grads)
+
+
+def pyramid_consistency_loss(outputs_list, n0, holder=None):
+    """URPC's regulariser (ssl_urpc.py:76-91) over the K = 2..4 full-resolution outputs [N, C, ...] of the joint batch: the
+    softmax of every scale, their mean, and per scale the KL-rectified squared error mean(sq * exp(-var)) / (mean(exp(-var)) +
+    1e-8) + mean(var) over the rows n0:, averaged over the scales.  The mean carries gradient, as in the reference.  holder: an
+    optional dict that receives the kernel's `out` (double [4 K + 2]: A_k, B_k, V_k, L_k per scale, loss_reg, 0).  Nothing is
+    read back to the host."""
+    if not isinstance(outputs_list, (list, tuple)):
+        raise ValueError("fplx ssl: pyramid_consistency_loss takes the LIST of a deep-supervised network's outputs "
+                         "([network] deep_supervise = True), got {0:}".format(type(outputs_list).__name__))
+    ts = list(outputs_list)
+    if not 2 <= len(ts) <= 4:
+        raise ValueError("fplx ssl: pyramid_consistency_loss takes 2 to 4 output scales, got {0:}".format(len(ts)))
+    for t in ts:
+        ops.require_gpu(t)
+        if t.dim() < 3:
+            raise ValueError("fplx ssl: every output must be [N, C, ...], got {0:}D".format(t.dim()))
+        if t.shape != ts[0].shape:
+            raise ValueError("fplx ssl: the output scales differ in shape ({0:} and {1:}); URPC compares full-resolution "
+                             "outputs".format(tuple(ts[0].shape), tuple(t.shape)))
+    n0 = int(n0)
+    if not 0 <= n0 < ts[0].shape[0]:
+        raise ValueError("fplx ssl: n0 = {0:} leaves no unlabelled row in a batch of {1:}".format(n0, ts[0].shape[0]))
+    return _Pyramid.apply(n0, holder, *ts)
+
+
+def cross_pseudo_labels(logits_list):
+    """CPS's pseudo labels (ssl_cps.py:103-106) for 1 to 3 logit tensors [N, C, ...] in one launch: detached fp32 one-hot tensors
+    of the first maximum of the logits over C"""
+    ts = [t.detach().float().contiguous() for t in logits_list]
+    with torch.no_grad():
+        return ops.ssl_pseudo_onehot(ts)
+
+
 _REFUSED_METHODS = ("CCT", "CPS", "URPC")
-_DSBN_NAMES = ("UNet2D5_dsbn", "UNet3D_dsbn")
 
 
 class SSLSegAgent(SegmentationAgent):
@@ -341,16 +407,135 @@ class SSLUncertaintyAwareMeanTeacher(SSLMeanTeacher):
         return consistency_loss(p1, teacher, mc, threshold)
 
 
+class SSLURPC(SSLSegAgent):
+    """ssl_urpc.py:14-122 on a deep-supervised UNet3D / UNet2D5 (four full-resolution outputs); the returned scalars are
+    _train_loop's: loss, loss_sup, loss_reg, regular_w, avg_dice, class_dice"""
+
+    def __init__(self, config, stage='train'):
+        if not config.get('network', {}).get('deep_supervise', False):
+            raise ValueError("fplx ssl: URPC compares the output scales of one network and needs a list of outputs: set "
+                             "[network] deep_supervise = True (UNet3D / UNet2D5 then return four full-resolution outputs)")
+        super(SSLURPC, self).__init__(config, stage)
+
+    def _regulariser(self, outputs, n0, x1, ramp):
+        return pyramid_consistency_loss(outputs, n0)
+
+
+class SSLCPS(SSLSegAgent):
+    """ssl_cps.py:31-176: two networks of [network] net_type in a BiNet, each supervised on the labelled rows and on the OTHER
+    one's pseudo labels of the unlabelled rows"""
+
+    def __init__(self, config, stage='train'):
+        if config.get('network', {}).get('deep_supervise', False):
+            raise ValueError("fplx ssl: CPS takes one output per network; with [network] deep_supervise = True the reference's "
+                             "torch.softmax(outputs1, dim=1) (ssl_cps.py:94) fails on a list - set deep_supervise = False")
+        super(SSLCPS, self).__init__(config, stage)
+        self.summ_writer = None           # tests / callers: an object with add_scalars(tag, dict, step), as the reference's
+
+    def create_network(self):
+        if self.net is None:
+            self.net = BiNet(self.config['network'], self.net_dict)
+        if self.tensor_type != 'float':
+            raise ValueError("fplx: tensor_type must be float (fp32 parameters)")
+        self.net.float()
+        self.net.to(self.device)
+
+    def create_optimizer(self, params=None):
+        opt_params = self.config['training']
+        if self.optimizer is None:
+            self.optimizer = GroupOptimizer([get_optimizer(opt_params['optimizer'], m, opt_params) for m in self.net.members()])
+        super(SSLCPS, self).create_optimizer(params)
+
+    def _train_loop(self, dual):
+        class_num = self.config['network']['class_num']
+        iter_valid = self.config['training']['iter_valid']
+        ssl_cfg = self.config['semi_supervised_learning']
+        if self.train_loader_unlab is None:
+            raise ValueError("fplx ssl: no unlabelled loader (create_dataset or set_unlabeled_loader)")
+        if getattr(self, '_unlab_iter', None) is None:
+            self._unlab_iter = iter(self.train_loader_unlab)
+        lab_iter = iter(self.train_loader_1)
+        self.net.train()
+        sums = None
+        dice = []
+        regular_w = 0.0
+        for _ in range(iter_valid):
+            data_lab, lab_iter = self._next(lab_iter, self.train_loader_1)
+            data_unlab, self._unlab_iter = self._next(self._unlab_iter, self.train_loader_unlab)
+            x0 = self.convert_tensor_type(data_lab['image']).to(self.device)
+            y0 = self.convert_tensor_type(data_lab['label_prob']).to(self.device)
+            x1 = self.convert_tensor_type(data_unlab['image']).to(self.device).contiguous()
+            n0 = x0.shape[0]
+            self.optimizer.zero_grad()
+            outputs1, outputs2 = self.net(torch.cat([x0, x1], dim=0))        # ONE forward over both batches, per network
+            loss_sup1 = self.get_loss_value(data_lab, outputs1[:n0], y0)
+            dice.append(self.loss_calculator.last_out[4:4 + class_num])     # hard Dice of net 1's labelled rows
+            loss_sup2 = self.get_loss_value(data_lab, outputs2[:n0], y0)
+            pse_prob1, pse_prob2 = cross_pseudo_labels([outputs1[n0:], outputs2[n0:]])
+            pse_sup1 = self.get_loss_value(data_unlab, outputs1[n0:], pse_prob2)
+            pse_sup2 = self.get_loss_value(data_unlab, outputs2[n0:], pse_prob1)
+            regular_w = ssl_cfg.get('regularize_w', 0.1) * self._ramp()
+            loss = (loss_sup1 + regular_w * pse_sup1) + (loss_sup2 + regular_w * pse_sup2)
+            loss.backward()
+            self.optimizer.step()
+            if self.scheduler is not None and not isinstance(self.scheduler, lr_scheduler.ReduceLROnPlateau):
+                self.scheduler.step()
+            row = torch.stack([loss.detach(), loss_sup1.detach(), loss_sup2.detach(), pse_sup1.detach(), pse_sup2.detach()])
+            sums = row if sums is None else sums + row
+        vals = (sums / iter_valid).cpu().numpy().astype(np.float64)          # the round's one host read
+        cls = torch.stack(dice).mean(0).cpu().numpy().astype(np.float64)
+        return {'loss': float(vals[0]), 'loss_sup1': float(vals[1]), 'loss_sup2': float(vals[2]), 'loss_pse_sup1': float(vals[3]),
+                'loss_pse_sup2': float(vals[4]), 'regular_w': regular_w, 'avg_dice': float(cls.mean()), 'class_dice': cls}
+
+    def write_scalars(self, train_scalars, valid_scalars, lr_value, glob_it):
+        """ssl_cps.py:152-176: the two log lines, and the same tags into `summ_writer` where one is attached"""
+        w = self.summ_writer
+        if w is not None:
+            w.add_scalars('loss', {'train': train_scalars['loss'], 'valid': valid_scalars['loss']}, glob_it)
+            w.add_scalars('loss_sup', {'net1': train_scalars['loss_sup1'], 'net2': train_scalars['loss_sup2']}, glob_it)
+            w.add_scalars('loss_pseudo_sup', {'net1': train_scalars['loss_pse_sup1'], 'net2': train_scalars['loss_pse_sup2']}, glob_it)
+            w.add_scalars('regular_w', {'regular_w': train_scalars['regular_w']}, glob_it)
+            w.add_scalars('lr', {"lr": lr_value}, glob_it)
+            w.add_scalars('dice', {'train': train_scalars['avg_dice'], 'valid': valid_scalars['avg_dice']}, glob_it)
+            for c in range(self.config['network']['class_num']):
+                w.add_scalars('class_{0:}_dice'.format(c), {'train': train_scalars['class_dice'][c],
+                                                            'valid': valid_scalars['class_dice'][c]}, glob_it)
+        for name, sc in (('train', train_scalars), ('valid', valid_scalars)):
+            logging.info('{0:} loss {1:.4f}, avg dice {2:.4f} '.format(name, sc['loss'], sc['avg_dice']) + "[" +
+                         ' '.join("{0:.4f}".format(x) for x in sc['class_dice']) + "]")
+
+    def train_valid(self):
+        history = super(SSLCPS, self).train_valid()
+        for glob_it, lr_value, train_scalars, valid_scalars in history:
+            self.write_scalars(train_scalars, valid_scalars, lr_value, glob_it)
+        return history
+
+
 SSLMethodDict = {'EntropyMinimization': SSLEntropyMinimization,
                  'MeanTeacher': SSLMeanTeacher,
                  'UAMT': SSLUncertaintyAwareMeanTeacher}
 
+# the first registry stays as the earlier suite pins it; this one holds every method that is built (the SegLossDict /
+# SegLossDictAll precedent)
+SSLMethodDictAll = dict(SSLMethodDict, CPS=SSLCPS, URPC=SSLURPC)
+
 
 def ssl_agent_class(name):
-    """ssl_main.py:16-21,42-43: the agent class of [semi_supervised_learning] ssl_method"""
+    """ssl_main.py:16-21,42-43: the agent class of [semi_supervised_learning] ssl_method among the first three methods"""
     if name in _REFUSED_METHODS:
         raise ValueError("fplx ssl: {0:} is not built: CCT, CPS and URPC need multi-decoder or two-branch networks the registry "
-                         "does not hold (SegNetDict has UNet2D5, UNet3D and the DSBN networks)".format(name))
+                         "does not hold (SegNetDict has UNet2D5, UNet3D and the DSBN networks); CPS and URPC are in "
+                         "SSLMethodDictAll / ssl_agent_class_all".format(name))
     if name not in SSLMethodDict:
         raise ValueError("Undefined semi-supervised method {0:}".format(name))
     return SSLMethodDict[name]
+
+
+def ssl_agent_class_all(name):
+    """the agent class among all five built methods; CCT is refused"""
+    if name == "CCT":
+        raise ValueError("fplx ssl: CCT is not built: its network with auxiliary decoders lives in pymic.net.net2d, a package "
+                         "the reference tree does not contain")
+    if name not in SSLMethodDictAll:
+        raise ValueError("Undefined semi-supervised method {0:}".format(name))
+    return SSLMethodDictAll[name]

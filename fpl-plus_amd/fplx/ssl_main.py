@@ -1,7 +1,7 @@
 """`python -m fplx.ssl_main train|test config.cfg` - the reference's `pymic_ssl` entry (PyMIC/pymic/net_run_ssl/ssl_main.py:23-44):
-parse + synchronize the .cfg, log to <ckpt_save_dir>/log_<stage>.txt, SSLMethodDict[ssl_method](config, stage).run().
+parse + synchronize the .cfg, log to <ckpt_save_dir>/log_<stage>.txt, SSLMethodDictAll[ssl_method](config, stage).run().
 Otherwise as fplx/net_run.py: after a training stage the test stage runs with the student's best checkpoint (through the
-supervised agent - a checkpoint holds the student only), then the evaluation reports are written."""
+supervised agent - a checkpoint holds the student only; CPS: through its own agent, the checkpoint holds the BiNet), then the evaluation reports are written."""
 import logging
 import os
 import sys
@@ -9,7 +9,7 @@ import sys
 from .agent import SegmentationAgent
 from .config import parse_config, synchronize_config
 from .net_run import eva_main
-from .ssl import ssl_agent_class
+from .ssl import SSLCPS, ssl_agent_class_all
 
 
 def main(argv=None):
@@ -30,11 +30,13 @@ def main(argv=None):
     config['network'].setdefault('num_domains', 1)
     if stage == 'train':
         ssl_method = config['semi_supervised_learning']['ssl_method']
-        agent = ssl_agent_class(ssl_method)(config, stage)
+        agent = ssl_agent_class_all(ssl_method)(config, stage)
         agent.run()
     if 'testing' in config:
         config['testing'].setdefault('domian_label', 0)
-        SegmentationAgent(config, 'test').run()
+        # a CPS checkpoint holds the whole BiNet (net1.*, net2.*): its test stage runs through the CPS agent, as fplx/nll_main.py
+        cps = config.get('semi_supervised_learning', {}).get('ssl_method', None) == 'CPS'
+        (SSLCPS if cps else SegmentationAgent)(config, 'test').run()
         return eva_main(config)
     return None
 

@@ -744,7 +744,22 @@ int fplx_add_noise_philox(const float* x, float* y, int64_t n, uint64_t seed, ui
  *             (Not the first family's entropy term: that one is log2 with + 1e-10, agent_seg.py:352-354.)
  *  ema_step:  ema = alpha ema + (1 - alpha) p over a flat fp32 segment, 0 <= alpha <= 1 (`ema_param.data.mul_(alpha).add_(1 -
  *             alpha, param.data)`, ssl_mt.py:112-113, for all parameters in one launch); 1 - alpha is formed in double on the
- *             host and rounded once, the element is fma(alpha, ema, (1 - alpha) p). */
+ *             host and rounded once, the element is fma(alpha, ema, (1 - alpha) p).
+ *  ssl_pyramid_fwd: URPC's regulariser (ssl_urpc.py:76-91) over K = 2..4 logit tensors given as a table of K device pointers,
+ *             each [N][C][V], N counting the unlabelled rows only.  Per voxel p_k = softmax(z_k), m = (p_1 + .. + p_K) / K,
+ *             a = 0.99 m + 0.005, q_k = 0.99 p_k + 0.005, var_k = sum_c a_c (ln a_c - ln q_kc), e_k = exp(-var_k),
+ *             s_k = sum_c (a_c - q_kc)^2.  part fp32 [N][fplx_loss_rows(V)][3 K].  With M = N V:
+ *             out double [K][4] + [2]: per scale A_k = sum s_k e_k, B_k = sum e_k, V_k = sum var_k,
+ *             L_k = (A_k / (C M)) / (B_k / M + 1e-8) + V_k / M; then loss_reg = (sum_k L_k) / K and 0.
+ *             The vector path takes four voxels per lane while K C <= 12, two beyond (K C values are live per voxel).
+ *  ssl_pyramid_bwd: one launch writes the K tensors dlogits_j = gscale[0] d loss_reg / d z_j.  With A_k, B_k read from `out` on
+ *             the device: alpha_k = 1 / (C M (B_k / M + 1e-8)), beta_k = -(A_k / (C M)) / (B_k / M + 1e-8)^2 / M,
+ *             g_k = 1 / M - e_k (alpha_k s_k + beta_k), h_k = alpha_k e_k,
+ *             dL/dp_jc = (0.99 / K) [(1 / K) sum_k (g_k (ln a_c - ln q_kc + 1) + 2 h_k (a_c - q_kc)) - g_j a_c / q_jc
+ *             - 2 h_j (a_c - q_jc)] (the mean m carries gradient, as in the reference), then the softmax Jacobian.
+ *  ssl_pseudo_onehot: K = 1..3 logit tensors (a pointer table) -> K fp32 one-hot tensors [N][C][V] of the FIRST maximum of the
+ *             logits over C: `get_soft_label(argmax(softmax(z)))` of ssl_cps.py:103-106 in one launch, except that two
+ *             distinct logits which fp32 softmax rounds to one probability keep their order here. */
 int fplx_ssl_perturb(const float* x, const float* noise, float* y, int64_t n, int reps, float sigma, float clip, uint64_t seed,
                      uint32_t stream_id, fplx_stream_t stream);
 int fplx_ssl_consistency_fwd(const float* student, const float* teacher, const float* mc, int t, int n, int c,
@@ -758,6 +773,12 @@ int fplx_ssl_entropy_fwd(const float* logits, int n, int c, int64_t voxels_per_s
 int fplx_ssl_entropy_bwd(const float* logits, const float* gscale, int n, int c, int64_t voxels_per_sample, int softmax,
                          float* dlogits, fplx_stream_t stream);
 int fplx_ema_step(float* ema, const float* p, int64_t n, float alpha, fplx_stream_t stream);
+int fplx_ssl_pyramid_fwd(const float* const* logits, int k, int n, int c, int64_t voxels_per_sample, float* part, double* out,
+                         fplx_stream_t stream);
+int fplx_ssl_pyramid_bwd(const float* const* logits, const double* out, const float* gscale, int k, int n, int c,
+                         int64_t voxels_per_sample, float* const* dlogits, fplx_stream_t stream);
+int fplx_ssl_pseudo_onehot(const float* const* logits, int k, int n, int c, int64_t voxels_per_sample, float* const* onehot,
+                           fplx_stream_t stream);
 
 /* ------------------------------------------------------------------ weakly-supervised learning (csrc/wsl.hip)
  * The regularisers of the reference's third entry point (PyMIC/pymic/net_run_wsl/; loss/seg/gatedcrf.py, loss/seg/ssl.py:46-86
