@@ -95,6 +95,25 @@ def prelu(x, slope):
     return torch.where(x > 0, x, zero) + neg * slope
 
 
+def tap(tape, kind, t):
+    """a decision tape (tests/kinkoracle.py) sees the tensor `t` of a site and may hand back another one; without a tape: t"""
+    return t if tape is None else tape.tap(kind, t)
+
+
+def act(tape, x, slope):
+    """PReLU (slope: the shared one-element tensor) or LeakyReLU (slope: a float), through the tape when there is one"""
+    if tape is not None:
+        return tape.act(x, slope)
+    return prelu(x, slope) if torch.is_tensor(slope) else F.leaky_relu(x, slope)
+
+
+def pool(tape, x):
+    """MaxPool2d / MaxPool3d(2, 2) of a 4-D / 5-D tensor, through the tape when there is one"""
+    if tape is not None:
+        return tape.pool(x)
+    return F.max_pool2d(x, 2, 2) if x.dim() == 4 else F.max_pool3d(x, 2, 2)
+
+
 def fold_depth(x):
     """DownBlock / UpBlock with dim == 2 (unet2d5_dsbn.py:110-115, 160-169): [N,C,D,H,W] -> [N*D,C,H,W]"""
     n, c, d, h, w = x.shape
@@ -112,15 +131,15 @@ def dsbn2d(x, sd, key, domain, train):
     return dsbn(x.unsqueeze(2), sd, key, domain, train).squeeze(2)
 
 
-def conv_block2d(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=None):
+def conv_block2d(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=None, tape=None):
     """ConvBlockND.forward, 2D branch (net3d/unet2d5_dsbn.py:66-73) on the depth-folded tensor.  keep_mask (if any) is
     given in the 5-D layout [N,C,D,H,W] like the 3D branch's and folded here."""
     if dropout_on is None:
         dropout_on = train
     x = F.conv2d(x, quant(sd[key + ".conv2d_1.weight"], act_dtype), sd[key + ".conv2d_1.bias"], padding=1)
-    x = quant(x, act_dtype)
+    x = tap(tape, "conv", quant(x, act_dtype))
     x = dsbn2d(x, sd, key + ".bn2d1", domain, train)
-    x = prelu(x, sd[key + ".relu_1.weight"])
+    x = act(tape, x, sd[key + ".relu_1.weight"])
     if p > 0 and dropout_on:
         if keep_mask is None:
             x = F.dropout(x, p, True)
@@ -129,21 +148,21 @@ def conv_block2d(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=
             x = x * fold_depth(keep_mask).to(x.dtype) * float(torch.tensor(1.0 / (1.0 - p32), dtype=torch.float32))
     x = quant(x, act_dtype)
     x = F.conv2d(x, quant(sd[key + ".conv2d_2.weight"], act_dtype), sd[key + ".conv2d_2.bias"], padding=1)
-    x = quant(x, act_dtype)
+    x = tap(tape, "conv", quant(x, act_dtype))
     x = dsbn2d(x, sd, key + ".bn2d2", domain, train)
-    x = prelu(x, sd[key + ".relu_2.weight"])
+    x = act(tape, x, sd[key + ".relu_2.weight"])
     return quant(x, act_dtype)
 
 
-def conv_block(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=None):
+def conv_block(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=None, tape=None):
     """ConvBlockND.forward, 3D branch (net3d/unet2d5_dsbn.py:74-81)."""
     if dropout_on is None:
         dropout_on = train
     # the HIP path packs convolution weights into the activation dtype (bf16 operands, fp32 accumulate)
     x = F.conv3d(x, quant(sd[key + ".conv3d_1.weight"], act_dtype), sd[key + ".conv3d_1.bias"], padding=1)
-    x = quant(x, act_dtype)
+    x = tap(tape, "conv", quant(x, act_dtype))
     x = dsbn(x, sd, key + ".bn3d1", domain, train)
-    x = prelu(x, sd[key + ".relu_1.weight"])
+    x = act(tape, x, sd[key + ".relu_1.weight"])
     if p > 0 and dropout_on:
         if keep_mask is None:
             x = F.dropout(x, p, True)
@@ -153,9 +172,9 @@ def conv_block(x, sd, key, domain, train, p, keep_mask, act_dtype, dropout_on=No
             x = x * keep_mask.to(x.dtype) * float(torch.tensor(1.0 / (1.0 - p32), dtype=torch.float32))
     x = quant(x, act_dtype)
     x = F.conv3d(x, quant(sd[key + ".conv3d_2.weight"], act_dtype), sd[key + ".conv3d_2.bias"], padding=1)
-    x = quant(x, act_dtype)
+    x = tap(tape, "conv", quant(x, act_dtype))
     x = dsbn(x, sd, key + ".bn3d2", domain, train)
-    x = prelu(x, sd[key + ".relu_2.weight"])
+    x = act(tape, x, sd[key + ".relu_2.weight"])
     return quant(x, act_dtype)
 
 
@@ -171,7 +190,7 @@ def block_dropout_p(net_params):
 
 
 def unet_forward(sd, net_params, x, domain, train=True, dropout_masks=None, act_dtype=None,
-                 dropout_on=None):
+                 dropout_on=None, tape=None):
     """UNet2D5_dsbn.forward (unet2d5_dsbn.py:296-309), both UpBlock forms (bilinear False / True); conv_dims[l] = 2 levels fold the depth axis
     into the batch and use the 2D members, exactly like DownBlock / UpBlock (108-129, 156-188).
 
@@ -179,7 +198,9 @@ def unet_forward(sd, net_params, x, domain, train=True, dropout_masks=None, act_
     domain: python int (= domain_label[0], dsbn.py:56).
     dropout_masks: optional list of 9 keep-masks (or None entries), one per ConvBlockND.
     dropout_on: dropout active (defaults to `train`); eval-mode BN + active dropout is the
-        FPL test-time setting (net_run_dsbn/agent_seg.py:843-852)."""
+        FPL test-time setting (net_run_dsbn/agent_seg.py:843-852).
+    tape: a decision tape (tests/kinkoracle.py) that every activation, pooling, skip and up-sampled tensor goes through;
+        None: the plain operators."""
     ps = block_dropout_p(net_params)
     masks = dropout_masks or [None] * 9
     dims = list(net_params.get("conv_dims", [3] * 5))
@@ -189,16 +210,16 @@ def unet_forward(sd, net_params, x, domain, train=True, dropout_masks=None, act_
     h = x
     for i in range(5):
         if dims[i] == 2:
-            h2 = conv_block2d(fold_depth(h), sd, BLOCK_KEYS[i], domain, train, ps[i], masks[i], act_dtype, dropout_on)
+            h2 = conv_block2d(fold_depth(h), sd, BLOCK_KEYS[i], domain, train, ps[i], masks[i], act_dtype, dropout_on, tape)
             h = unfold_depth(h2, n)
             if i < 4:
                 skips.append(h)
-                h = unfold_depth(F.max_pool2d(h2, 2, 2), n)              # DownBlock, line 104/117
+                h = unfold_depth(pool(tape, h2), n)                     # DownBlock, line 104/117
         else:
-            h = conv_block(h, sd, BLOCK_KEYS[i], domain, train, ps[i], masks[i], act_dtype, dropout_on)
+            h = conv_block(h, sd, BLOCK_KEYS[i], domain, train, ps[i], masks[i], act_dtype, dropout_on, tape)
             if i < 4:
                 skips.append(h)
-                h = F.max_pool3d(h, 2, 2)                               # DownBlock, line 106/117
+                h = pool(tape, h)                                       # DownBlock, line 106/117
     bilinear = bool(net_params.get("bilinear", False))
     for j in range(4):
         key = "up%d" % (j + 1)
@@ -209,29 +230,31 @@ def unet_forward(sd, net_params, x, domain, train=True, dropout_masks=None, act_
                 up = F.conv2d(fold_depth(h), quant(sd[key + ".conv2d.weight"], act_dtype), sd[key + ".conv2d.bias"])
                 up = quant(up, act_dtype)
                 up = quant(F.interpolate(up, scale_factor=2, mode="bilinear", align_corners=True), act_dtype)
-                hc = torch.cat([fold_depth(skips[3 - j]), up], dim=1)
+                up = tap(tape, "up", up)
+                hc = torch.cat([fold_depth(tap(tape, "skip", skips[3 - j])), up], dim=1)
                 h = unfold_depth(conv_block2d(hc, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype,
-                                              dropout_on), n)
+                                              dropout_on, tape), n)
             else:
                 up = F.conv3d(h, quant(sd[key + ".conv3d.weight"], act_dtype), sd[key + ".conv3d.bias"])
                 up = quant(up, act_dtype)
                 up = quant(F.interpolate(up, scale_factor=2, mode="trilinear", align_corners=True), act_dtype)
-                h = torch.cat([skips[3 - j], up], dim=1)
-                h = conv_block(h, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype, dropout_on)
+                up = tap(tape, "up", up)
+                h = torch.cat([tap(tape, "skip", skips[3 - j]), up], dim=1)
+                h = conv_block(h, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype, dropout_on, tape)
             continue
         if dims[3 - j] == 2:
             up = F.conv_transpose2d(fold_depth(h), quant(sd[key + ".trans2d.weight"], act_dtype),
                                     sd[key + ".trans2d.bias"], stride=2)   # line 179
-            up = quant(up, act_dtype)
-            hc = torch.cat([fold_depth(skips[3 - j]), up], dim=1)       # line 182
+            up = tap(tape, "up", quant(up, act_dtype))
+            hc = torch.cat([fold_depth(tap(tape, "skip", skips[3 - j])), up], dim=1)       # line 182
             h = unfold_depth(conv_block2d(hc, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype,
-                                          dropout_on), n)
+                                          dropout_on, tape), n)
             continue
         up = F.conv_transpose3d(h, quant(sd[key + ".trans3d.weight"], act_dtype), sd[key + ".trans3d.bias"],
                                 stride=2)                                  # line 181
-        up = quant(up, act_dtype)
-        h = torch.cat([skips[3 - j], up], dim=1)                        # line 182
-        h = conv_block(h, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype, dropout_on)
+        up = tap(tape, "up", quant(up, act_dtype))
+        h = torch.cat([tap(tape, "skip", skips[3 - j]), up], dim=1)                        # line 182
+        h = conv_block(h, sd, BLOCK_KEYS[5 + j], domain, train, ps[5 + j], masks[5 + j], act_dtype, dropout_on, tape)
     return F.conv3d(h, sd["out_conv.weight"], sd["out_conv.bias"], padding=(0, 1, 1))  # lines 293-294, 307
 
 

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle.torch_ref import quant, split_state, prelu, fold_depth, unfold_depth, dice_loss, BN_EPS, BN_MOMENTUM  # noqa: F401
+from oracle.torch_ref import tap, act, pool
 
 
 def batch_norm(x, sd, key, train, unrounded=None):
@@ -33,25 +34,25 @@ def batch_norm(x, sd, key, train, unrounded=None):
     return (x - mean.view(sh)) * torch.rsqrt(var.view(sh) + BN_EPS) * sd[key + ".weight"].view(sh) + sd[key + ".bias"].view(sh)
 
 
-def conv_block(x, sd, key, train, act_dtype, leaky):
+def conv_block(x, sd, key, train, act_dtype, leaky, tape=None):
     """`conv_conv` (unet3d.py:20-28 with LeakyReLU, unet2d5.py:22-40 with PReLU; dropout 0): 2D when the weights are"""
     conv = F.conv2d if sd[key + ".0.weight"].dim() == 4 else F.conv3d
     rounding = act_dtype is not None and act_dtype != torch.float32
     for c, b, a in ((0, 1, 2), (4, 5, 6)):
         y = conv(x, quant(sd["%s.%d.weight" % (key, c)], act_dtype), sd["%s.%d.bias" % (key, c)], padding=1)
-        x = batch_norm(quant(y, act_dtype), sd, "%s.%d" % (key, b), train, y if rounding else None)
-        x = F.leaky_relu(x, 0.01) if leaky else prelu(x, sd["%s.%d.weight" % (key, a)])
+        x = batch_norm(tap(tape, "conv", quant(y, act_dtype)), sd, "%s.%d" % (key, b), train, y if rounding else None)
+        x = act(tape, x, 0.01 if leaky else sd["%s.%d.weight" % (key, a)])
         x = quant(x, act_dtype)
     return x
 
 
-def unet3d_forward(sd, params, x, train=True, act_dtype=None, round_input=True):
+def unet3d_forward(sd, params, x, train=True, act_dtype=None, round_input=True, tape=None):
     """UNet3D.forward (unet3d.py:137-160) -> tensor, or the list of four with deep supervision"""
     L = len(params["feature_chns"])
     x = quant(x, act_dtype) if round_input else x
-    xs = [conv_block(x, sd, "in_conv.conv_conv", train, act_dtype, True)]
+    xs = [conv_block(x, sd, "in_conv.conv_conv", train, act_dtype, True, tape)]
     for i in range(1, L):
-        xs.append(conv_block(F.max_pool3d(xs[-1], 2), sd, "down%d.maxpool_conv.1.conv_conv" % i, train, act_dtype, True))
+        xs.append(conv_block(pool(tape, xs[-1]), sd, "down%d.maxpool_conv.1.conv_conv" % i, train, act_dtype, True, tape))
     h = xs[-1]
     xd = {L - 1: h}
     for l in range(L - 2, -1, -1):
@@ -61,19 +62,20 @@ def unet3d_forward(sd, params, x, train=True, act_dtype=None, round_input=True):
             up = quant(F.interpolate(up, scale_factor=2, mode="trilinear", align_corners=True), act_dtype)
         else:
             up = quant(F.conv_transpose3d(h, quant(sd[key + ".up.weight"], act_dtype), sd[key + ".up.bias"], stride=2), act_dtype)
-        h = conv_block(torch.cat([xs[l], up], dim=1), sd, key + ".conv.conv_conv", train, act_dtype, True)
+        h = conv_block(torch.cat([tap(tape, "skip", xs[l]), tap(tape, "up", up)], dim=1), sd, key + ".conv.conv_conv", train, act_dtype,
+                       True, tape)
         xd[l] = h
     out = F.conv3d(xd[0], sd["out_conv.weight"], sd["out_conv.bias"])
     if not params["deep_supervise"]:
         return out
     outs = [out]
     for l in (1, 2, 3):
-        o = F.conv3d(xd[l], sd["out_conv%d.weight" % l], sd["out_conv%d.bias" % l])
+        o = F.conv3d(tap(tape, "head", xd[l]), sd["out_conv%d.weight" % l], sd["out_conv%d.bias" % l])
         outs.append(F.interpolate(o, list(out.shape[2:]), mode="trilinear"))
     return outs
 
 
-def unet2d5_forward(sd, params, x, train=True, act_dtype=None, round_input=True):
+def unet2d5_forward(sd, params, x, train=True, act_dtype=None, round_input=True, tape=None):
     """UNet2D5.forward (unet2d5.py:199-211): a conv_dims = 2 level folds the depth axis into the batch (67-88, 122-142)"""
     dims, bilinear = list(params["conv_dims"]), bool(params["bilinear"])
     n = x.shape[0]
@@ -82,16 +84,16 @@ def unet2d5_forward(sd, params, x, train=True, act_dtype=None, round_input=True)
     for i in range(5):
         key = "block%d.conv.conv_conv" % i
         if dims[i] == 2:
-            h2 = conv_block(fold_depth(h), sd, key, train, act_dtype, False)
+            h2 = conv_block(fold_depth(h), sd, key, train, act_dtype, False, tape)
             h = unfold_depth(h2, n)
             if i < 4:
                 skips.append(h)
-                h = unfold_depth(F.max_pool2d(h2, 2, 2), n)
+                h = unfold_depth(pool(tape, h2), n)
         else:
-            h = conv_block(h, sd, key, train, act_dtype, False)
+            h = conv_block(h, sd, key, train, act_dtype, False, tape)
             if i < 4:
                 skips.append(h)
-                h = F.max_pool3d(h, 2, 2)
+                h = pool(tape, h)
     for j in range(4):
         l = 3 - j
         key = "up%d" % (j + 1)
@@ -104,18 +106,21 @@ def unet2d5_forward(sd, params, x, train=True, act_dtype=None, round_input=True)
         else:
             tr = F.conv_transpose2d if two else F.conv_transpose3d
             up = quant(tr(hin, quant(sd[key + ".up.weight"], act_dtype), sd[key + ".up.bias"], stride=2), act_dtype)
-        skip = fold_depth(skips[l]) if two else skips[l]
-        h = conv_block(torch.cat([skip, up], dim=1), sd, key + ".conv.conv_conv", train, act_dtype, False)
+        skip = tap(tape, "skip", skips[l])
+        skip = fold_depth(skip) if two else skip
+        h = conv_block(torch.cat([skip, tap(tape, "up", up)], dim=1), sd, key + ".conv.conv_conv", train, act_dtype, False, tape)
         if two:
             h = unfold_depth(h, n)
     return F.conv3d(h, sd["out_conv.weight"], sd["out_conv.bias"], padding=(0, 1, 1))
 
 
-def forward(sd, params, x, train=True, act_dtype=None, round_input=True):
-    """round_input: the first convolution rounds the fp32 network input to bf16 - true of the MFMA stem kernels (bf16 operands),
+def forward(sd, params, x, train=True, act_dtype=None, round_input=True, tape=None):
+    """tape: a decision tape (tests/kinkoracle.py) for the activations, poolings, skip, up-sampled and head-input tensors; None:
+    the plain operators.
+    round_input: the first convolution rounds the fp32 network input to bf16 - true of the MFMA stem kernels (bf16 operands),
     not of the generic kernel that serves a stem they do not take (it reads the input as stored, fp32)"""
     fn = unet3d_forward if params["net_type"] == "UNet3D" else unet2d5_forward
-    return fn(sd, params, x, train, act_dtype, round_input)
+    return fn(sd, params, x, train, act_dtype, round_input, tape)
 
 
 def deep_supervise_loss(preds, base, weights=None):

@@ -12,7 +12,9 @@ from util import load_det_weights, max_rel, plan_kernel
 
 pytestmark = pytest.mark.gpu
 
-# max-normalised gradient tolerance: see tests/test_oracle_golden.py (reference's own fp32 noise) x2
+# max-normalised gradient tolerance: see tests/test_oracle_golden.py (the reference's own movement under another summation
+# order, x2).  What moves is a decision - one PReLU sign or pooling winner at a near-tie - not BatchNorm round-off: against float64
+# with the device's own decisions forced the same gradients are within 4e-5 .. 1e-3 (tests/test_gpu_net_backward_exact.py)
 GRAD_TOL = {"tiny": 1e-3, "tiny25": 1e-2, "c4": 1e-3, "cfg1": 1e-2, "tinybl": 1e-3, "tinybl25": 4e-2}
 LOGIT_TOL = 1e-3            # north_star: logits within 1e-3 in fp32
 

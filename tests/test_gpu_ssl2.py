@@ -146,7 +146,8 @@ def _params(deep):
 def _weights(member, deep):
     """member 0: the fixture's draw; member 1: every float tensor nudged by the draw `cps2` (variances kept positive).  The draw
     `nll1` is not used: tests/test_gpu_nll.py records that UNet3D's parameter gradients differ from tests/nets3d_ref.py by up to
-    1.4e-2 with it (an open finding of the network's backward, not of this feature)."""
+    1.4e-2 with it - one LeakyReLU sign that the device and the CPU take differently, not a fault of the backward
+    (tests/test_gpu_net_backward_exact.py, case u3d4_ds.plain.nll1)."""
     import detdata
     w = dict(C.weights_for(NAME))
     if not deep:

@@ -16,8 +16,12 @@ torch.set_num_threads(max(1, (os.cpu_count() or 2) // 2))
 
 
 # max-normalised gradient tolerance: the fp32 reference itself moves by this much when only the
-# CPU thread count (= summation order) changes (BN over few voxels at the deepest level)
-GRAD_TOL = {"tiny": 5e-4, "tiny25": 5e-3, "c4": 5e-4, "cfg1": 5e-3, "tinybl": 5e-4, "tinybl25": 2e-2}   # tinybl25: BatchNorm over 16 voxels at level 4 amplifies fp32 round-off
+# CPU thread count (= summation order) changes.  BatchNorm over few voxels does not amplify round-off to this size: another
+# summation order turns ONE PReLU sign or pooling winner whose margin is inside the round-off (1 or 2 of up to 11.5 M
+# decisions), and a gradient follows its decisions.  With the decisions pinned the fp32 arithmetic is within 1e-4 of
+# float64 in every config (tests/test_kink_oracle_cpu.py prints both columns).  A comparison of two FREE evaluations,
+# as here, needs the loose values; tests/test_gpu_net_backward_exact.py holds the tight ones.
+GRAD_TOL = {"tiny": 5e-4, "tiny25": 5e-3, "c4": 5e-4, "cfg1": 5e-3, "tinybl": 5e-4, "tinybl25": 2e-2}
 
 
 def _load(golden_dir, name):
