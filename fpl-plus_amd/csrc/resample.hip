@@ -19,30 +19,11 @@
 // tests/test_gpu_resample.py holds the result to scipy's bits.
 //
 // One thread per output voxel, W fastest (coalesced stores), all channels in one launch; the gather side relies on L2.
-#include "common.h"
+#include "resample_common.h"      // RsGeo, rs_coord, rs_inside, rs_extents_ok: shared with spline.hip
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)     // (the header sets it too: it holds the coordinate sum)
 
 namespace {
-
-constexpr int RS_THREADS = 256;
-constexpr int64_t RS_MAX_ELEMS = (int64_t)1 << 31;      // 32-bit linear indices inside the kernel
-
-struct RsGeo {
-  double m[3][3];
-  double t[3];
-  int C, D, H, W, OD, OH, OW;
-};
-
-__device__ __forceinline__ double rs_coord(const double* __restrict__ m, double t, double o0, double o1, double o2) {
-  double c = o0 * m[0];
-  c = c + o1 * m[1];
-  c = c + o2 * m[2];
-  return c + t;
-}
-
-// !(c >= 0 && c <= n - 1): a NaN coordinate (non-finite matrix) counts as outside, so that no index is ever formed from it
-__device__ __forceinline__ bool rs_inside(double c, int n) { return c >= 0.0 && c <= (double)(n - 1); }
 
 template <typename T, int ORDER>
 __global__ void __launch_bounds__(RS_THREADS)
@@ -84,16 +65,6 @@ resample_affine_k(const T* __restrict__ x, T* __restrict__ y, const RsGeo g) {
   }
 }
 
-inline bool rs_extents_ok(int c, int d, int h, int w) {
-  if (c <= 0 || d <= 0 || h <= 0 || w <= 0) return false;
-  int64_t n = c;                                              // every partial product stays below 2^62
-  for (int e : {d, h, w}) {
-    n *= e;
-    if (n >= RS_MAX_ELEMS) return false;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -108,12 +79,7 @@ int fplx_resample_affine(const void* x, void* y, int elem_bytes, int order, int 
   FPLX_REQUIRE(elem_bytes == 4 || elem_bytes == 1, FPLX_E_BADDTYPE, "resample_affine: element size %d (4 fp32, 1 uint8)",
                elem_bytes);
   FPLX_REQUIRE(elem_bytes == 4 || order == 0, FPLX_E_BADDTYPE, "resample_affine: uint8 volumes take order 0 only");
-  RsGeo g;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) g.m[i][j] = matrix9[3 * i + j];
-    g.t[i] = offset3[i];
-  }
-  g.C = c; g.D = d; g.H = h; g.W = w; g.OD = od; g.OH = oh; g.OW = ow;
+  const RsGeo g = rs_geo(c, d, h, w, od, oh, ow, matrix9, offset3);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)c * od * oh * ow;
   const unsigned grid = (unsigned)((total + RS_THREADS - 1) / RS_THREADS);

@@ -29,7 +29,7 @@ from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMum
                   WSLMethodDict, TotalVariationLoss, MumfordShahLoss, GatedCRFLoss)
 from .nll import (NLLSegAgent, NLLCoTeaching, NLLTriNet, NLLMethodDict, nll_agent_class, BiNet, TriNet,          # noqa: E402
                   GroupOptimizer, selective_ce_loss)
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup         # noqa: E402
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup, resample   # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -45,4 +45,5 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "wsl", "WSLSegAgent", "WSLEntropyMinimization", "WSLTotalVariation", "WSLMumfordShah", "WSLGatedCRF", "WSLUSTM",
            "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss",
            "nll", "NLLSegAgent", "NLLCoTeaching", "NLLTriNet", "NLLMethodDict", "nll_agent_class", "BiNet", "TriNet",
-           "GroupOptimizer", "selective_ce_loss"]
+           "GroupOptimizer", "selective_ce_loss",
+           "resample"]

@@ -914,6 +914,51 @@ def resample_affine(x, matrix, offset, out_size, order):
     return y
 
 
+SPLINE_ORDERS = (3,)          # the spline orders csrc/spline.hip builds (its table has one row per order)
+
+
+def _check_spline_volume(x, who, order):
+    require_gpu(x)
+    if not (x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("fplx: {0:} takes a contiguous [C,D,H,W] volume".format(who))
+    if x.dtype != torch.float32:
+        raise ValueError("fplx: {0:} takes float32 volumes, got {1:}".format(who, x.dtype))
+    if int(order) not in SPLINE_ORDERS:
+        raise ValueError("fplx: {0:}: spline order {1:} is not built (built: {2:})".format(
+            who, order, ", ".join(str(o) for o in SPLINE_ORDERS)))
+
+
+def spline_prefilter(x, order=3):
+    """B-spline coefficients (float64 [C,D,H,W]) of a float32 [C,D,H,W] volume under scipy's mirror boundary:
+    scipy.ndimage.spline_filter(x, order, output=float64, mode='mirror') along D, H and W"""
+    _check_spline_volume(x, "spline_prefilter", order)
+    c, d, h, w = x.shape
+    coef = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+    call("fplx_spline_prefilter", ptr(x), ptr(coef), c, d, h, w, int(order), stream())
+    return coef
+
+
+def resample_spline(x, matrix, offset, out_size, order=3):
+    """y[c][o] = spline(x[c], matrix o + offset) for a float32 [C,D,H,W] volume -> [C,*out_size]: scipy.ndimage's affine
+    resampling at spline order 3 (mode='constant', cval=0): the prefilter, then the 64-tap interpolation.  matrix (3x3) and
+    offset (3) are host numbers, taken as fp64."""
+    _check_spline_volume(x, "resample_spline", order)
+    m = [float(v) for row in matrix for v in row]
+    t = [float(v) for v in offset]
+    if len(m) != 9 or len(t) != 3 or len(out_size) != 3:
+        raise ValueError("fplx: resample_spline takes a 3x3 matrix, a 3-vector offset and a 3D output size")
+    c, d, h, w = x.shape
+    od, oh, ow = (int(v) for v in out_size)
+    y = torch.empty((c, max(od, 0), max(oh, 0), max(ow, 0)), dtype=torch.float32, device=x.device)
+    if min(c, d, h, w) > 0 and min(od, oh, ow) > 0:
+        coef = spline_prefilter(x, order)
+    else:
+        coef = torch.empty(x.shape, dtype=torch.float64, device=x.device)      # the library refuses the extents below
+    call("fplx_resample_spline", ptr(coef), ptr(y), c, d, h, w, od, oh, ow, (ctypes.c_double * 9)(*m),
+         (ctypes.c_double * 3)(*t), int(order), stream())
+    return y
+
+
 def label_bbox(label, mask_labels):
     """-> (count, bb_min[4], bb_max[4]) of {label in mask_labels} on a uint8 [C,D,H,W] label (one device->host copy)"""
     require_gpu(label)

@@ -603,6 +603,29 @@ int fplx_paste_roi(const void* sub, void* out, int elem_bytes, int c, int sd, in
 int fplx_resample_affine(const void* x, void* y, int elem_bytes, int order, int c, int d, int h, int w, int od, int oh,
                          int ow, const double* matrix9, const double* offset3, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ dataset preparation: cubic-spline resampling
+ * scipy.ndimage.zoom / rotate / affine_transform at their default spline order 3, which the reference's preparation uses
+ * (data/preprocess_vs.py:107-135: ndimage.zoom(img_sub, zoom); PyMIC/pymic/util/image_process.py:210-228: any order).
+ * Two steps, as in scipy; fplx.ops.resample_spline runs both.
+ *
+ * fplx_spline_prefilter: x [c][d][h][w] fp32 -> coef [c][d][h][w] fp64, the B-spline coefficients under scipy's mirror
+ *  boundary: the recursive filter with pole z = sqrt(3) - 2 along every line of D, then H, then W.  Per line of length
+ *  n > 1: c *= (1 - z)(1 - 1/z);  c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1..n-2} z^i (c[i] + z^(n-1) c[n-1-i])) /
+ *  (1 - z^(2n-2));  c[i] += z c[i-1];  c[n-1] = (z c[n-2] + c[n-1]) z / (z z - 1);  c[i] = z (c[i+1] - c[i]) downwards; a
+ *  line of length 1 is left alone.  All sums run in that one order, without atomics: bitwise reproducible.  x and coef
+ *  must not overlap.
+ * fplx_resample_spline: y[ch][o] = sum over the 4x4x4 taps of coef * w_d * w_h * w_w at M o + t in fp64, one cast to fp32;
+ *  coordinates and the outside rule (c_i < 0, c_i > n_i - 1 or NaN -> 0) are fplx_resample_affine's; taps floor(c) - 1 + k,
+ *  k = 0..3, reflected about the first and last sample (period 2n - 2; an axis of extent 1 reads index 0); weights with
+ *  y = c - floor(c), zc = 1 - y: w1 = (y y (y - 2) 3 + 4) / 6, w2 = (zc zc (zc - 2) 3 + 4) / 6, w0 = zc zc zc / 6,
+ *  w3 = 1 - w0 - w1 - w2; the value is multiplied by one axis weight after the other, k_d outermost, k_w innermost.
+ *  matrix9 and offset3 are HOST arrays of doubles, read before the call returns; coef and y must not overlap.
+ * Refused before any launch: FPLX_E_NULL for a missing pointer; FPLX_E_BADSHAPE for a non-positive extent, 2^31 elements or
+ * more on either side, or an order other than 3 (orders 2, 4 and 5 are not built; the message names the built order). */
+int fplx_spline_prefilter(const float* x, double* coef, int c, int d, int h, int w, int order, fplx_stream_t stream);
+int fplx_resample_spline(const double* coef, float* y, int c, int d, int h, int w, int od, int oh, int ow,
+                         const double* matrix9, const double* offset3, int order, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ Inferer: sliding window + flip TTA
  * PyMIC/pymic/net_run_dsbn/infer_func.py:50-112 (tiling, overlap averaging), 188-222 (tta_mode 1).
  * The tile grid is the Cartesian product of per-axis start lists (HOST arrays, at most 64 entries each, non-decreasing,
