@@ -29,7 +29,8 @@ from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMum
                   WSLMethodDict, TotalVariationLoss, MumfordShahLoss, GatedCRFLoss)
 from .nll import (NLLSegAgent, NLLCoTeaching, NLLTriNet, NLLMethodDict, nll_agent_class, BiNet, TriNet,          # noqa: E402
                   GroupOptimizer, selective_ce_loss)
-from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup, resample   # noqa: E402
+from .image_process import distance_transform_edt, get_euclidean_distance                                   # noqa: E402
+from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup, resample, image_process   # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
            "CrossEntropyLoss", "DiceLoss_weight", "CombinedLoss", "EntropyTerm", "make_loss", "Inferer",
@@ -46,4 +47,4 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss",
            "nll", "NLLSegAgent", "NLLCoTeaching", "NLLTriNet", "NLLMethodDict", "nll_agent_class", "BiNet", "TriNet",
            "GroupOptimizer", "selective_ce_loss",
-           "resample"]
+           "resample", "image_process", "distance_transform_edt", "get_euclidean_distance"]

@@ -959,6 +959,73 @@ def resample_spline(x, matrix, offset, out_size, order=3):
     return y
 
 
+EDT_LINES = 32                # EDT_LINES of csrc/edt.hip: the lines a block stages in LDS
+EDT_MAX_EXTENT = 620          # FPLX_EDT_MAX_EXTENT of include/fplx.h: the longest line whose tile fits the 160 KiB of LDS
+
+
+def edt_sampling(sampling, ndim):
+    """scipy's `sampling` argument -> ndim floats: None is 1 per axis, a scalar is repeated, a sequence needs ndim entries"""
+    if sampling is None:
+        return [1.0] * ndim
+    s = [float(v) for v in np.atleast_1d(np.asarray(sampling, np.float64)).ravel()]
+    if len(s) == 1:
+        s = s * ndim
+    if len(s) != ndim:
+        raise ValueError("fplx: sampling has {0:} entries for a {1:}D input".format(len(s), ndim))
+    return s
+
+
+def edt_squared(mask, sampling=None, return_indices=False, batched=False):
+    """squared Euclidean distance (float64, mask's shape) of every voxel of a uint8 mask [D,H,W] or [H,W] (batched=True: a
+    leading batch dimension in front) to the nearest zero voxel under `sampling`: scipy.ndimage.distance_transform_edt
+    before its square root, bit for bit.  A mask without a zero gets scipy's result, the distance to index (-1, 0, 0).
+    return_indices: also int32 [ndim, ...] ([N, ndim, ...] when batched), the coordinates of a zero voxel at that distance"""
+    require_gpu(mask)
+    nd = mask.dim() - (1 if batched else 0)
+    if nd not in (2, 3):
+        raise ValueError("fplx: edt_squared takes a 2D or 3D mask, got {0:}D".format(nd))
+    if not (mask.dtype == torch.uint8 and mask.is_contiguous()):
+        raise ValueError("fplx: edt_squared takes a contiguous uint8 mask")
+    s = edt_sampling(sampling, nd)
+    n = mask.shape[0] if batched else 1
+    d, h, w = ((1,) if nd == 2 else ()) + tuple(mask.shape[-nd:])
+    if min(n, d, h, w) > 0:
+        phantom = (mask.reshape(n, -1).amin(dim=1) != 0).to(torch.uint8)      # a device flag per mask: no host round trip
+    else:
+        phantom = None                                                          # the library refuses the extents below
+    sq = torch.empty(mask.shape, dtype=torch.float64, device=mask.device)
+    idx = ws = None
+    if return_indices:
+        lead = (n,) if batched else ()
+        idx = torch.empty(lead + (nd,) + tuple(mask.shape[-nd:]), dtype=torch.int32, device=mask.device)
+        ws = torch.empty(2 * mask.numel(), dtype=torch.int32, device=mask.device)
+    call("fplx_edt_squared", ptr(mask), n, d, h, w, nd, (ctypes.c_double * 3)(*([1.0] * (3 - nd) + s)), ptr(phantom), ptr(sq),
+         ptr(idx), ptr(ws), 0 if ws is None else ws.numel() * 4, stream())
+    return (sq, idx) if return_indices else sq
+
+
+def edt_pass(g, axis, sampling=1.0):
+    """one pass of the transform IN PLACE on a float64 map [N,D,H,W] along axis 0 (D), 1 (H) or 2 (W):
+    g[j] = min_i (g[i] + ((j - i) * sampling)^2) on every line (+inf allowed); returns g"""
+    require_gpu(g)
+    if not (g.dim() == 4 and g.dtype == torch.float64 and g.is_contiguous()):
+        raise ValueError("fplx: edt_pass takes a contiguous float64 [N,D,H,W] map")
+    n, d, h, w = g.shape
+    call("fplx_edt_pass", ptr(g), n, d, h, w, int(axis), float(sampling), stream())
+    return g
+
+
+def edt_finish(sq_a, sq_b=None):
+    """sqrt(sq_a), or with sq_b the signed map sqrt(sq_b) - sqrt(sq_a) of get_euclidean_distance; float64 in and out"""
+    require_gpu(sq_a, sq_b)
+    for t in (sq_a, sq_b):
+        if t is not None and not (t.dtype == torch.float64 and t.is_contiguous() and t.shape == sq_a.shape):
+            raise ValueError("fplx: edt_finish takes contiguous float64 maps of one shape")
+    out = torch.empty_like(sq_a)
+    call("fplx_edt_finish", ptr(sq_a), ptr(sq_b), ptr(out), sq_a.numel(), stream())
+    return out
+
+
 def label_bbox(label, mask_labels):
     """-> (count, bb_min[4], bb_max[4]) of {label in mask_labels} on a uint8 [C,D,H,W] label (one device->host copy)"""
     require_gpu(label)

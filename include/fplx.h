@@ -626,6 +626,39 @@ int fplx_spline_prefilter(const float* x, double* coef, int c, int d, int h, int
 int fplx_resample_spline(const double* coef, float* y, int c, int d, int h, int w, int od, int oh, int ow,
                          const double* matrix9, const double* offset3, int order, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ exact Euclidean distance transform
+ * scipy.ndimage.distance_transform_edt, which get_euclidean_distance calls on image > 0.5 and on image <= 0.5
+ * (PyMIC/pymic/util/image_process.py:165-192); fplx.image_process mirrors both.
+ *
+ * fplx_edt_squared: mask uint8 [n][d][h][w] (nonzero = foreground; ndim = 2: a 2D mask, d must be 1) -> sq fp64 [n][d][h][w],
+ *  the SQUARED distance of every voxel to the nearest background voxel of its mask under the sampling (sz, sy, sx)
+ *  (sampling3: HOST array of 3 doubles, read before the call returns; ndim = 2 uses sampling3[1] and [2] only; all three must be valid): with g0 = 0 on
+ *  background and +inf on foreground, for axis 0, then 1, then 2: g[j] = min_i (g[i] + ((j - i) s_axis)^2) - product, square,
+ *  sum, each rounded to fp64, none contracted - which equals scipy's min over the background of
+ *  ((dz sz)^2 + (dy sy)^2) + (dx sx)^2 bit for bit.  Background voxels get exactly 0.  No atomics: bitwise reproducible.
+ *  phantom: device uint8 [n] or NULL; phantom[m] != 0 states that mask m has NO background voxel (the caller's reduction):
+ *  the result is then scipy's, the distance to one background voxel at index (-1, 0, 0) (2D: (-1, 0)).  A mask without
+ *  background whose flag is not set yields +inf everywhere.
+ *  idx: NULL, or int32 [n][ndim][d][h][w], the feature transform: the coordinates (z, y, x) (2D: (y, x)) of a background voxel
+ *  at that distance ((-1, 0, 0) under phantom); among several at the same distance scipy may name another.  It needs
+ *  ws: int32 workspace of at least FPLX_EDT_WS_BYTES(n, d * h * w) bytes (unused and may be NULL when idx is NULL).
+ * fplx_edt_pass: ONE of those passes alone, in place on a fp64 map g [n][d][h][w] along axis 0 (d), 1 (h) or 2 (w) with the
+ *  sampling of that axis: g[j] = min_i (g[i] + ((j - i) s)^2) on every line; +inf entries are allowed, a line without a
+ *  finite entry stays +inf.  The three calls on g0 reproduce fplx_edt_squared for a mask with background; the benchmark
+ *  (tools/edt_bench.py) times the passes with it.
+ * fplx_edt_finish: out[i] = sqrt(sq_a[i]) when sq_b is NULL, else sqrt(sq_b[i]) - sqrt(sq_a[i]) (the signed map of
+ *  get_euclidean_distance: a = image > 0.5, b = image <= 0.5, both from ONE fplx_edt_squared call with n = 2), i < count;
+ *  out must not overlap the inputs.
+ * Refused before any launch: FPLX_E_NULL for a missing pointer; FPLX_E_BADSHAPE for a non-positive extent, an extent above
+ * FPLX_EDT_MAX_EXTENT (a block stages whole lines in LDS; the message names the limit), 2^31 elements or more, ndim other than
+ * 2 or 3, an axis other than 0..2, or a sampling that is not positive and finite; FPLX_E_WORKSPACE for a workspace that is too small. */
+#define FPLX_EDT_MAX_EXTENT 620
+#define FPLX_EDT_WS_BYTES(n, voxels) ((size_t)2 * (size_t)(n) * (size_t)(voxels) * 4)
+int fplx_edt_squared(const uint8_t* mask, int n, int d, int h, int w, int ndim, const double* sampling3, const uint8_t* phantom,
+                     double* sq, int* idx, int* ws, size_t ws_bytes, fplx_stream_t stream);
+int fplx_edt_pass(double* g, int n, int d, int h, int w, int axis, double sampling, fplx_stream_t stream);
+int fplx_edt_finish(const double* sq_a, const double* sq_b, double* out, int64_t count, fplx_stream_t stream);
+
 /* ------------------------------------------------------------------ Inferer: sliding window + flip TTA
  * PyMIC/pymic/net_run_dsbn/infer_func.py:50-112 (tiling, overlap averaging), 188-222 (tta_mode 1).
  * The tile grid is the Cartesian product of per-axis start lists (HOST arrays, at most 64 entries each, non-decreasing,
