@@ -30,6 +30,10 @@ from .wsl import (WSLSegAgent, WSLEntropyMinimization, WSLTotalVariation, WSLMum
 from .nll import (NLLSegAgent, NLLCoTeaching, NLLTriNet, NLLMethodDict, nll_agent_class, BiNet, TriNet,          # noqa: E402
                   GroupOptimizer, selective_ce_loss)
 from .image_process import distance_transform_edt, get_euclidean_distance                                   # noqa: E402
+from .confident import (get_confident_map, get_noise_indices, compute_confident_joint, calibrate_confident_joint,   # noqa: E402
+                        keep_at_least_n_per_class, round_preserving_sum)
+from .nll_clslsr import NLLCLSLSR, get_confidence_map                                                        # noqa: E402
+from . import confident, nll_clslsr                                                                          # noqa: E402
 from . import filter, ops, ddp, transform, nifti, evaluation, postprocess, ssl, wsl, nll, netgroup, resample, image_process   # noqa: E402
 
 __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDict", "DiceLoss",
@@ -47,4 +51,6 @@ __all__ = ["UNet2D5_dsbn", "DomainSpecificBatchNorm3d", "SegLossDict", "SegNetDi
            "WSLMethodDict", "TotalVariationLoss", "MumfordShahLoss", "GatedCRFLoss",
            "nll", "NLLSegAgent", "NLLCoTeaching", "NLLTriNet", "NLLMethodDict", "nll_agent_class", "BiNet", "TriNet",
            "GroupOptimizer", "selective_ce_loss",
-           "resample", "image_process", "distance_transform_edt", "get_euclidean_distance"]
+           "resample", "image_process", "distance_transform_edt", "get_euclidean_distance",
+           "confident", "nll_clslsr", "get_confident_map", "get_noise_indices", "compute_confident_joint",
+           "calibrate_confident_joint", "keep_at_least_n_per_class", "round_preserving_sum", "NLLCLSLSR", "get_confidence_map"]

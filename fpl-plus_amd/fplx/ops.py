@@ -1551,3 +1551,85 @@ def nll_select_bwd(logits_list, label, masks, uses, out, gscale, wj, dlogits=Non
     call("fplx_nll_select_bwd", _ptrs(ls), ptr(label), _ptrs(masks), (ctypes.c_int * k)(*[int(u) for u in uses]), k, ptr(out),
          ptr(gscale), float(wj), n, c, v, _ptrs(dlogits), stream())
     return dlogits
+
+
+# ---- confident learning (csrc/cl.hip): psx fp32 planar [C, M], s uint8 [M]; every cut stays on the device
+
+CL_BY_CLASS, CL_BY_NOISE_RATE, CL_BOTH = 0, 1, 2
+
+
+def _cl_planar(psx, s=None, what="psx"):
+    """-> (c, m) of a planar [C, M] float32 tensor whose class planes are contiguous and follow each other (a view at an
+    offset is fine: the kernels fall back to one voxel per lane where a base is not 16-byte aligned)"""
+    require_gpu(psx, s)
+    if not (psx.dtype == torch.float32 and psx.dim() == 2 and psx.numel() > 0 and psx.is_contiguous()):
+        raise ValueError("fplx cl: {0:} must be a non-empty contiguous float32 tensor [C, M]".format(what))
+    c, m = int(psx.shape[0]), int(psx.shape[1])
+    if s is not None and not (s.dtype == torch.uint8 and s.dim() == 1 and s.numel() == m and s.is_contiguous()):
+        raise ValueError("fplx cl: the labels must be a contiguous uint8 tensor of {0:} elements".format(m))
+    return c, m
+
+
+def cl_softmax(x, out=None):
+    """logits fp32 planar [C, M] -> psx of that shape, the max-subtracted fp32 softmax over the classes, written once"""
+    c, m = _cl_planar(x, what="the logits")
+    out = torch.empty_like(x) if out is None else out
+    if _cl_planar(out, what="out") != (c, m):
+        raise ValueError("fplx cl_softmax: out has another shape than the logits")
+    call("fplx_cl_softmax", ptr(x), c, m, ptr(out), stream())
+    return out
+
+
+def cl_class_stats(psx, s):
+    """-> (sums float64 [C], counts int64 [C + 2], thr float64 [C]) on the device: counts[k] = #{s == k}, counts[C] = #{s >= C},
+    counts[C + 1] = #{voxels with a NaN}; sums[k] = the float64 sum of psx[k] over s == k; thr = sums / counts"""
+    c, m = _cl_planar(psx, s)
+    dev = psx.device
+    nb = _lib.lib().fplx_cl_stats_ws_bytes()
+    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    sums = torch.empty(c, dtype=torch.float64, device=dev)
+    thr = torch.empty(c, dtype=torch.float64, device=dev)
+    counts = torch.empty(c + 2, dtype=torch.int64, device=dev)
+    call("fplx_cl_class_stats", ptr(psx), ptr(s), c, m, ptr(ws), ws.numel() * 8, ptr(sums), ptr(counts), ptr(thr), stream())
+    return sums, counts, thr
+
+
+def cl_confident_joint(psx, s, thr):
+    """-> joint int64 [C, C] on the device: joint[s][guess] over the voxels with a confident class (thr: device float64 [C])"""
+    c, m = _cl_planar(psx, s)
+    require_gpu(thr)
+    if not (thr.dtype == torch.float64 and thr.numel() == c and thr.is_contiguous()):
+        raise ValueError("fplx cl_confident_joint: thr must be a contiguous float64 tensor of {0:} elements".format(c))
+    joint = torch.empty((c, c), dtype=torch.int64, device=psx.device)
+    call("fplx_cl_confident_joint", ptr(psx), ptr(s), c, m, ptr(thr), ptr(joint), stream())
+    return joint
+
+
+def cl_select_keys(psx, s, k, j=-1, out=None):
+    """-> keys fp32 [M] for select_kth: psx[k] (j < 0) or -(psx[j] - psx[k]) where s == k, NaN elsewhere"""
+    c, m = _cl_planar(psx, s)
+    out = torch.empty(m, dtype=torch.float32, device=psx.device) if out is None else _chan(out)
+    if out.numel() != m:
+        raise ValueError("fplx cl_select_keys: out has {0:} elements for {1:} voxels".format(out.numel(), m))
+    call("fplx_cl_select_keys", ptr(psx), ptr(s), c, m, int(k), int(j), ptr(out), stream())
+    return out
+
+
+def cl_noise_mask(psx, s, method, class_cut=None, pair_cut=None, pair_active=None):
+    """-> (mask uint8 [M], count int64 [1]) on the device.  class_cut fp32 [C] and pair_cut fp32 [C, C] are device tensors,
+    pair_active a host array [C, C] (pair_cut[k, j] is read where pair_active[k, j])"""
+    c, m = _cl_planar(psx, s)
+    require_gpu(class_cut, pair_cut)
+    for t, n, what in ((class_cut, c, "class_cut"), (pair_cut, c * c, "pair_cut")):
+        if t is not None and not (t.dtype == torch.float32 and t.numel() == n and t.is_contiguous()):
+            raise ValueError("fplx cl_noise_mask: {0:} must be a contiguous float32 tensor of {1:} elements".format(what, n))
+    act = None
+    if pair_active is not None:
+        act = np.ascontiguousarray(np.asarray(pair_active) != 0, np.uint8)
+        if act.shape != (c, c):
+            raise ValueError("fplx cl_noise_mask: pair_active must be [{0:}, {0:}]".format(c))
+    mask = torch.empty(m, dtype=torch.uint8, device=psx.device)
+    count = torch.empty(1, dtype=torch.int64, device=psx.device)
+    call("fplx_cl_noise_mask", ptr(psx), ptr(s), c, m, int(method), ptr(class_cut), ptr(pair_cut),
+         None if act is None else act.ctypes.data, ptr(mask), ptr(count), stream())
+    return mask, count

@@ -929,6 +929,44 @@ int fplx_nll_select_bwd(const float* const* logits, const float* label, const ui
                         const double* out, const float* gscale, float wj, int n, int c, int64_t voxels_per_sample,
                         float* const* dlogits, fplx_stream_t stream);
 
+/* ------------------------------------------------------------------ confident learning (csrc/cl.hip)
+ * The producer of the mask SLSRLoss smooths with: what the reference's get_confident_map (PyMIC/pymic/net_run_nll/nll_clslsr.py:
+ * 19-46) gets from cleanlab 1.0's get_noise_indices, as streaming passes.  psx fp32 PLANAR [C][M] (class plane c contiguous),
+ * s uint8 [M] the given labels, 2 <= C <= 8, 1 <= M < 2^31 (the bound of fplx_select_kth).  A lane takes four voxels with 16-byte
+ * accesses where the fp32 bases are 16-byte aligned, the byte arrays 4-byte aligned and M is a multiple of 4, else one voxel.
+ * fp32 values are summed in double; block partials are added in a fixed order by one wave; counts are integers (integer
+ * atomics) - no floating-point atomics, two runs give the same bits.  FPLX_E_NULL / FPLX_E_BADSHAPE / FPLX_E_WORKSPACE before
+ * any launch.  A voxel with s >= C takes part in nothing but counts[C].
+ *  cl_softmax: p[c][i] = softmax over c of x[.][i] in fp32: max, expf(x - max), the sum with c ascending, one division.  Written
+ *             once; every later pass reads these stored bits, none recomputes them.
+ *  cl_class_stats: counts int64 [C + 2]: counts[k] = #{s == k}, counts[C] = #{s >= C}, counts[C + 1] = #{voxels with a NaN in any
+ *             plane}.  sums double [C]: sums[k] = sum over s_i == k of double(psx[k][i]).  thr double [C] (may be NULL) =
+ *             sums[k] / counts[k], one division.  ws: at least fplx_cl_stats_ws_bytes(), 8-byte aligned; ONE launch after a memset
+ *             node that clears its ticket.
+ *  cl_confident_joint: conf_k = double(psx[k][i]) >= thr[k] - 1e-6 (float64).  No confident class: not counted; one: guess is that
+ *             class; several: guess = the first maximum of psx[.][i] over ALL classes.  joint int64 [C][C]: joint[s_i][guess] += 1.
+ *             joint is cleared by a memset node in front of the launch.
+ *  cl_select_keys: j < 0: keys[i] = psx[k][i] where s_i == k, NaN elsewhere.  j >= 0 (j != k): keys[i] = -(psx[j][i] - psx[k][i])
+ *             there (one fp32 rounding, the negation exact).  NaN sorts last in fplx_select_kth, so rank r of keys is rank r
+ *             among the members for r < counts[k].
+ *  cl_noise_mask: mask uint8 [M], count int64 [1] = the number of set voxels (cleared by a memset node).  With k = s_i:
+ *             by_class = psx[k][i] < class_cut[k]; by_rate = some j with pair_active[k][j] and psx[j][i] - psx[k][i] >=
+ *             pair_cut[k][j] (fp32, as the keys); mask = (by_class | by_rate | both of them, by `method`) and the first maximum
+ *             of psx[.][i] != k.  class_cut fp32 [C] and pair_cut fp32 [C][C] are DEVICE arrays (the values fplx_select_kth wrote,
+ *             pair_cut with the sign of the margin restored); pair_active uint8 [C][C] is a HOST array read before the call
+ *             returns, its diagonal ignored.  A table the method does not use may be NULL.  Comparisons are on values, so
+ *             voxels that tie at a cut are kept or dropped together. */
+enum { FPLX_CL_BY_CLASS = 0, FPLX_CL_BY_NOISE_RATE = 1, FPLX_CL_BOTH = 2 };
+int fplx_cl_softmax(const float* x, int c, int64_t m, float* p, fplx_stream_t stream);
+size_t fplx_cl_stats_ws_bytes(void);
+int fplx_cl_class_stats(const float* psx, const uint8_t* s, int c, int64_t m, void* ws, size_t ws_bytes, double* sums,
+                        int64_t* counts, double* thr, fplx_stream_t stream);
+int fplx_cl_confident_joint(const float* psx, const uint8_t* s, int c, int64_t m, const double* thr, int64_t* joint,
+                            fplx_stream_t stream);
+int fplx_cl_select_keys(const float* psx, const uint8_t* s, int c, int64_t m, int k, int j, float* keys, fplx_stream_t stream);
+int fplx_cl_noise_mask(const float* psx, const uint8_t* s, int c, int64_t m, int method, const float* class_cut,
+                       const float* pair_cut, const uint8_t* pair_active, uint8_t* mask, int64_t* count, fplx_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
