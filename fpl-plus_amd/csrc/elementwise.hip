@@ -1167,7 +1167,10 @@ static int maxpool_bwd_impl(const void* x, int64_t ldx, const void* dy, int64_t 
                             void* dx, int64_t ldo, int n, int d, int h, int w, int c, int dt, int pd, fplx_stream_t stream) {
   FPLX_REQUIRE(x && dy && dx, FPLX_E_NULL, "maxpool2_bwd: null pointer");
   FPLX_REQUIRE(n > 0 && c > 0 && d >= pd && h >= 2 && w >= 2 && !(d % pd) && !(h & 1) && !(w & 1), FPLX_E_BADSHAPE,
-               "maxpool2_bwd: bad shape");
+               "maxpool2_bwd: bad shape (even %sH,W required) %dx%dx%d", pd == 2 ? "D," : "", d, h, w);
+  FPLX_REQUIRE(ldx >= c && ldy >= c && (!dskip || lds >= c) && ldo >= c, FPLX_E_BADSHAPE,
+               "maxpool2_bwd: a leading dimension (%lld, %lld, %lld, %lld) is smaller than C = %d", (long long)ldx,
+               (long long)ldy, (long long)lds, (long long)ldo, c);
   hipStream_t st = (hipStream_t)stream;
   const int64_t vo = (int64_t)n * (d / pd) * (h / 2) * (w / 2);
   if (dt == FPLX_F32) {
