@@ -501,6 +501,7 @@ int fplx_wsl_tv_fwd(const float* logits, int n, int c, int d, int h, int w, int 
   const int64_t v = (int64_t)d * h * w, e = (int64_t)n * c * v;
   FPLX_REQUIRE(ws_bytes >= (size_t)e * 12, FPLX_E_BADSHAPE, "wsl_tv_fwd: workspace of %zu bytes, %lld needed", ws_bytes,
                (long long)e * 12);
+  FPLX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15u) == 0, FPLX_E_BADSHAPE, "wsl_tv_fwd: the workspace is not 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   float* pp = (float*)ws;
   float* er = pp + e;

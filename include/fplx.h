@@ -858,7 +858,8 @@ int fplx_ssl_pseudo_onehot(const float* const* logits, int k, int n, int c, int6
  *             in-bounds 3x3x3 window, o_v = max of e over the in-bounds window, contour_v = relu(o_v - e_v); out0 = sum contour,
  *             out3 = N C D H W, out2 = out0 / out3.  count int32 [N][C][D][H][W]: every voxel with contour_v > 0 adds +1 at the
  *             p' voxel whose value o_v is and -1 at the argmin of its own window; equal values take the first in (d, h, w) scan
- *             order, as torch's pooling does.  ws: at least 12 N C D H W bytes (p', e, the argmin offsets), 16-byte aligned.
+ *             order, as torch's pooling does.  ws: at least 12 N C D H W bytes (p', e, the argmin offsets), 16-byte aligned
+ *             (FPLX_E_BADSHAPE otherwise).
  *             part: fp32 [N C][fplx_loss_rows(D H W)].
  *  wsl_tv_bwd: e_c = 0.999 count_c / (N C D H W).
  *  wsl_mumford_shah_fwd: MumfordShahLoss.forward.  Per slice, class c, image channel ch: S0 = sum p_c, S1 = sum I_ch p_c over
